@@ -8,13 +8,14 @@ per-GPU micro-batch 8, data parallel (weak scaling), bf16 trunk / fp32 trainable
 weights at true dimensions.
 
 One step = forward of the whole path + backward through the trainable tail + gradient all-reduce + AdamW step.
-Launch:  python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: re-executes itself under
-                                                                 torch.distributed.run with N ranks on 127.0.0.1)
+Launch:  python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: runs itself under torch.distributed.run
+                                                                 with N ranks on 127.0.0.1, as a child process)
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line.  The line never claims a GPU count other than the one asked for: `--gpus N` with WORLD_SIZE != N is
 refused, and `rccl_ranks` is what the RCCL communicator itself reports (ncclCommCount through the C ABI's mp_comm_count).
 `--dry` runs the launch / rendezvous / timing / one-line protocol on CPU ranks over gloo with a stand-in gradient bucket (no GPU,
-no model): what tests/test_bench_launch.py drives."""
+no model): what tests/test_bench_launch.py drives.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy,
+so that two builds can be compared output for output."""
 import argparse
 import json
 import os
@@ -431,6 +432,31 @@ def lora_secondary(args, device, ds_config, synthetic_batch, rank, steps=8, warm
     return res
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6      # --dump-outputs writes at most this much in all
+DUMP_SAMPLE = 8 * 10**6            # an output with more elements is written as a fixed, seeded sample of this many
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: every array as `dirpath/<name>.npy`, float64 kept, anything else as float32.  An array of more than DUMP_SAMPLE
+    elements is flattened and cut to the elements at the sorted positions `numpy.random.default_rng(0).choice(n, DUMP_SAMPLE,
+    replace=False)`: the same positions for the same n, so two runs, or two builds, compare element for element."""
+    out = {}
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().to(torch.float64 if a.dtype == torch.float64 else torch.float32).cpu().numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        out[name] = a
+    total = sum(a.nbytes + 256 for a in out.values())         # + a bound on the .npy header
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def claim_stdout():
     """stdout carries ONE JSON line and nothing else: fd 1 is pointed at stderr for the life of the process (RCCL prints a version banner
     to the C stdout of every rank, flushed at exit — i.e. after the line) and the returned function writes to the original stdout."""
@@ -444,10 +470,11 @@ def claim_stdout():
 
 
 def ensure_ranks(want, dry):
-    """`--gpus N` must mean N ranks.  No launcher in the environment and N > 1: replace this process by
+    """`--gpus N` must mean N ranks.  No launcher in the environment and N > 1: run
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same flags>`
-    (the reference's launch line is `deepspeed --include localhost:0..7 train_ds_medplib.py`, scripts/train_stage3.sh).  A launcher
-    that started a different number of ranks is an error, not a smaller benchmark."""
+    as a child process and exit with its status (the reference's launch line is `deepspeed --include localhost:0..7 train_ds_medplib.py`,
+    scripts/train_stage3.sh).  A child, not an exec: the device count above may already have opened the HIP runtime in this process.
+    A launcher that started a different number of ranks is an error, not a smaller benchmark."""
     world = os.environ.get("WORLD_SIZE")
     if world is None and want > 1:
         if not dry and torch.cuda.device_count() < want:
@@ -460,7 +487,8 @@ def ensure_ranks(want, dry):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={want}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush(); sys.stderr.flush()
-        os.execvpe(cmd[0], cmd, env)
+        import subprocess
+        sys.exit(subprocess.call(cmd, env=env))
     if int(world or 1) != want:
         sys.exit(f"bench.py: --gpus {want} but the launcher started WORLD_SIZE={world} rank(s); refusing to report n_gpus != requested")
 
@@ -530,6 +558,8 @@ def dry_main(args, emit):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(allok, op=dist.ReduceOp.MIN)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"bucket": eng.optimizer.flat_grad})
         dt = tmax.item()
         extra = {}
         if epx is not None:
@@ -588,6 +618,11 @@ def main():
     ap.add_argument("--ep-comm", default="torch", choices=("torch", "capi"),
                     help="with --ep: the exchange through torch.distributed's all_to_all_single (default) or the C ABI's mp_alltoall_tokens")
     ap.add_argument("--dry", action="store_true", help="CPU ranks over gloo, stand-in gradient bucket: the launch / timing / one-line protocol only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the LAST timed step computed as DIR/<name>.npy (float32): every loss of the "
+                         "dict the model returned and `trainable_params`, the flat trainable parameter buffer after the step's AdamW update (a fixed, "
+                         "seeded sample when it is larger than 8 M elements); with --dry the reduced gradient bucket.  The inputs and weights are "
+                         "seeded, so two runs with the same arguments compare output for output")
     args = ap.parse_args()
     if args.ep and args.gpus % args.ep:
         sys.exit(f"bench.py: --ep {args.ep} does not divide --gpus {args.gpus}")
@@ -765,6 +800,9 @@ def gpu_main(args, emit):
     dt = time.perf_counter() - t0
     mark(2)
     ops.GEMM_TIMER = None
+    if args.dump_outputs and rank == 0:
+        # here, before the roofline steps below update the parameters again
+        dump_outputs(args.dump_outputs, {**{k: out[k] for k in out}, "trainable_params": eng.optimizer.flat_param})
     ep_obj = None
     if epx is not None:
         us = [s0.elapsed_time(e0) * 1e3 for _, s0, e0 in epx.timing]

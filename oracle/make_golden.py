@@ -876,6 +876,35 @@ def golden_evaluate():
     print("evaluate goldens ok:", os.path.getsize(os.path.join(OUT, "lisa_evaluate_reference.npz")) // 1024, "KiB")
 
 
+def deepspeed_ckpt_case(directory):
+    """A seeded synthetic DeepSpeed `global_step` directory: the dense model_states file, two expert files and an optimizer-states file
+    that is not a *model_states.pt file.  -> the dense state dict.  tests/test_host_logic.py builds its case with this too."""
+    g = torch.Generator().manual_seed(0)
+    dense = {"model.embed_tokens.weight": torch.randn(10, 4, generator=g).to(torch.bfloat16),
+             "model.layers.0.self_attn.q_proj.weight": torch.randn(4, 4, generator=g).to(torch.bfloat16),
+             "model.layers.0.mlp.deepspeed_moe.gate.wg.weight": torch.randn(2, 4, generator=g)}
+    torch.save({"module": dense, "global_steps": 7}, os.path.join(directory, "mp_rank_00_model_states.pt"))
+    for e in range(2):
+        torch.save({f"model.layers.0.mlp.deepspeed_moe.experts.deepspeed_experts.{e}.up_proj.weight": torch.randn(8, 4, generator=g).to(torch.bfloat16)},
+                   os.path.join(directory, f"layer_0_expert_{e}_mp_rank_00_model_states.pt"))
+    torch.save({"x": 1}, os.path.join(directory, "bf16_zero_pp_rank_0_mp_rank_00_optim_states.pt"))
+    return dense
+
+
+def golden_ckpt_merge():
+    """The reference's own params_bf16_to_f32.load_model_parameters executed on deepspeed_ckpt_case: the merged fp32 state dict."""
+    import importlib.util
+    import tempfile
+    spec = importlib.util.spec_from_file_location("ref_params_bf16_to_f32", os.path.join(REF, "params_bf16_to_f32.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    with tempfile.TemporaryDirectory() as d:
+        deepspeed_ckpt_case(d)
+        ref = mod.load_model_parameters(d, "cpu")
+    # sorted: the reference walks os.listdir order, the fixture's bytes must not depend on it
+    np.savez_compressed(os.path.join(OUT, "ckpt_merge_reference.npz"), **{k: ref[k].numpy() for k in sorted(ref)})
+
+
 def golden_llama_layer():
     """One dense decoder layer + final norm at the 7B dims (d 4096, ff 11008, 32 heads x 128, S 639, one right-padded sample) run by
     the installed HuggingFace `LlamaModel` — the class the reference's dense path instantiates (medplib_llama.py:32-37,98-107) — on
@@ -929,3 +958,5 @@ if __name__ == "__main__":
         golden_llama_layer()
     if "evaluate" in which:
         golden_evaluate()
+    if "ckpt_merge" in which:
+        golden_ckpt_merge()

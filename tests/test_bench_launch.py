@@ -1,5 +1,5 @@
 """CPU: bench.py's multi-rank launch contract.  `python bench.py --gpus N` with no launcher in the environment must produce N ranks
-by itself (re-exec under torch.distributed.run on 127.0.0.1) and print one JSON line whose n_gpus is N; a launcher that started
+by itself (a child process under torch.distributed.run on 127.0.0.1) and print one JSON line whose n_gpus is N; a launcher that started
 another number of ranks is refused.  `--dry` = gloo ranks and a stand-in gradient bucket through the engine's reduce path."""
 import json
 import os
@@ -24,6 +24,20 @@ def test_bench_gpus_2_self_launches_two_ranks():
     r = json.loads(lines[0])
     assert r["n_gpus"] == 2 and r["ranks"] == 2 and r["steps"] == 4 and r["warmup"] == 1 and r["bucket_sums_correct"] is True
     assert r["config"]["parallelism"] == "dp2" and r["dry"] is True
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes what the last timed step computed as float32 .npy files.  Dry step k fills rank r's bucket with
+    r + 1 + k, so after --steps 4 on two ranks the reduced bucket holds (0 + 1 + 3) + (1 + 1 + 3) = 9 everywhere — and --steps set the count."""
+    import numpy as np
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], env=_clean_env(), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert r["steps"] == 4 and r["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path / "out")) == ["bucket.npy"]
+    b = np.load(tmp_path / "out" / "bucket.npy")
+    assert b.dtype == np.float32 and b.shape == (64 * 32 + 32,) and np.all(b == 9.0)
 
 
 def test_bench_refuses_a_rank_count_other_than_requested():

@@ -10,7 +10,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TARGETS = ["sam", "mask_head", "glue", "collate", "preprocess", "dataset", "lisa", "llama_layer", "evaluate"]
+TARGETS = ["sam", "mask_head", "glue", "collate", "preprocess", "dataset", "lisa", "llama_layer", "evaluate", "ckpt_merge"]
 
 
 def _md5(path):

@@ -498,32 +498,20 @@ def test_collate_contract():
     assert lengths == [4, 2, 4, 4, 2, 4] and bases == [0, 16, 4, 8, 18, 12]
 
 
-def test_deepspeed_checkpoint_merge_matches_executed_reference(tmp_path):
-    """merge_deepspeed_states vs the reference's own `params_bf16_to_f32.load_model_parameters`, executed on the same synthetic
-    DeepSpeed directory when /root/reference is present (this container); the fixed expectations below hold everywhere."""
-    import importlib.util
+def test_deepspeed_checkpoint_merge_matches_executed_reference(tmp_path, golden_dir):
+    """merge_deepspeed_states vs the reference's own `params_bf16_to_f32.load_model_parameters`, executed on the same synthetic DeepSpeed
+    directory (oracle/make_golden.py: deepspeed_ckpt_case; its optimizer-states file is not a *model_states.pt file and is ignored) and
+    stored as tests/golden/ckpt_merge_reference.npz; the fixed expectations below hold besides."""
     from medplib_amd import checkpoint as C
-    g = torch.Generator().manual_seed(0)
+    from oracle.make_golden import deepspeed_ckpt_case
     d = tmp_path / "global_step7"
     d.mkdir()
-    dense = {"model.embed_tokens.weight": torch.randn(10, 4, generator=g).to(torch.bfloat16),
-             "model.layers.0.self_attn.q_proj.weight": torch.randn(4, 4, generator=g).to(torch.bfloat16),
-             "model.layers.0.mlp.deepspeed_moe.gate.wg.weight": torch.randn(2, 4, generator=g)}
-    torch.save({"module": dense, "global_steps": 7}, d / "mp_rank_00_model_states.pt")
-    for e in range(2):
-        torch.save({f"model.layers.0.mlp.deepspeed_moe.experts.deepspeed_experts.{e}.up_proj.weight": torch.randn(8, 4, generator=g).to(torch.bfloat16)},
-                   d / f"layer_0_expert_{e}_mp_rank_00_model_states.pt")
-    torch.save({"x": 1}, d / "bf16_zero_pp_rank_0_mp_rank_00_optim_states.pt")            # not a *model_states.pt file: ignored
+    dense = deepspeed_ckpt_case(str(d))
     merged = C.merge_deepspeed_states(str(d))
     assert len(merged) == 5 and all(v.dtype == torch.float32 for v in merged.values())
     assert torch.equal(merged["model.layers.0.self_attn.q_proj.weight"], dense["model.layers.0.self_attn.q_proj.weight"].float())
-    ref_path = "/root/reference/params_bf16_to_f32.py"
-    if os.path.exists(ref_path):
-        spec = importlib.util.spec_from_file_location("ref_params_bf16_to_f32", ref_path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        ref = mod.load_model_parameters(str(d), "cpu")
-        assert set(ref) == set(merged) and all(torch.equal(ref[k], merged[k]) for k in ref)
+    ref = np.load(os.path.join(golden_dir, "ckpt_merge_reference.npz"))
+    assert set(ref.files) == set(merged) and all(torch.equal(torch.from_numpy(ref[k]), merged[k]) for k in ref.files)
     # a key present in two files is an error, like the reference
     torch.save({"model.embed_tokens.weight": torch.zeros(1)}, d / "layer_0_expert_9_mp_rank_00_model_states.pt")
     with pytest.raises(ValueError):
