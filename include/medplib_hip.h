@@ -109,6 +109,15 @@ int mp_gemm_bf16_nt_batched_rows(const void* A, int64_t lda, int64_t strideA, co
 int mp_gemv_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy, const float* bias,
                  const void* residual, int64_t ldr, const int* w_index, const float* row_scale, const int* row_keep, int M, int N, int K,
                  int act, int out_dtype, float alpha, hipStream_t stream);
+/* Top-2 MoE decode rows (tokens <= 8), the expert GEMVs over the 2 * tokens entries of mp_moe_route_top2's layout (entry c * tokens + t =
+ * choice c of token t; expert[e], slot[e] < 0 = dropped, weight[e]).  gate|up: act[e, :N/2] = SwiGLU-paired x[t] . W[expert[e]] (W [E, N, K]
+ * interleaved gate|up rows; dropped entries are skipped and their rows left unwritten).  down: y[t] = residual[t] + sum over the kept choices
+ * in order of weight[e] * bf16(act[e] . W[expert[e]]) — mp_moe_combine_bf16's order and rounding points — in one launch. */
+int mp_gemv_top2_gate_up_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* act, int64_t ldact,
+                              const int* expert, const int* slot, int tokens, int N, int K, hipStream_t stream);
+int mp_gemv_top2_down_bf16(const void* act, int64_t ldact, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy,
+                           const void* residual, int64_t ldr, const int* expert, const int* slot, const float* weight, int tokens, int N,
+                           int K, hipStream_t stream);
 /* mp_rmsnorm_bf16 (HF LlamaRMSNorm, medplib_moe_llama.py:121 / :286) folded into the GEMV that consumes it: y[m, :] = rmsnorm(x[m, :]) @ W^T,
  * bit-identical with the two separate calls.  Decode steps: input_layernorm -> the fused q|k|v projection, and (dense layers)
  * post_attention_layernorm -> the interleaved gate|up projection with act = SWIGLU_PAIR (y [M, N/2]).  1 <= M <= 2; K a multiple of 512
@@ -356,6 +365,12 @@ int mp_moe_fill_dropped_bf16(const void* x, const int* slot, void* out, int64_t 
 int mp_decode_norm_gate_route(const void* x, int64_t ldx, const float* ln_w, float eps, const float* wg, void* h, int64_t ldh,
                               const float* rts_uniform, int tokens, int dim, int n_experts, int capacity, float* gates, int* expert,
                               int* slot, float* weight, int* kept_counts, long long* exp_counts, float* l_aux, hipStream_t stream);
+/* Decode rows (tokens <= 8), top-2 routing: the post-attention LlamaRMSNorm, the TopKGate logits / softmax and top2gating in one launch —
+ * bit-identical with mp_rmsnorm_bf16 + mp_moe_gate_bf16 + mp_moe_route_top2 (same tie rules: first index wins).  noise (optional)
+ * [tokens, n_experts]: the Gumbel draws of the second choice.  expert / slot / weight [2 * tokens] in mp_moe_route_top2's entry layout. */
+int mp_decode_norm_gate_route_top2(const void* x, int64_t ldx, const float* ln_w, float eps, const float* wg, void* h, int64_t ldh,
+                                   const float* noise, int tokens, int dim, int n_experts, int capacity, int* expert, int* slot,
+                                   float* weight, int* kept_counts, long long* exp_counts, float* l_aux, hipStream_t stream);
 /* DeepSpeed residual MoE (MoE(use_residual=True).forward, deepspeed/moe/layer.py; off in the shipped scripts,
  * train_ds_medplib.py:131): out = x + (moe * c0 + mlp * c1), (c0, c1) = softmax of the two `coefficient` logits of the row
  * (coef [tokens, ldcoef >= 2] bf16), with the bf16 module's rounding points. */
@@ -371,6 +386,9 @@ int mp_moe_route_top2(const float* gates, const float* logits, const float* nois
 /* Stateless draws for the gate: U(0,1) (RTS, top1gating) or Gumbel(0,1) (gumbel != 0; top2gating second-expert sampling)
  * from a hash of (seed, offset + i).  DeepSpeed uses torch's generator for these: same distribution, different stream. */
 int mp_gate_noise_f32(float* out, int64_t n, uint64_t seed, uint64_t offset, int gumbel, hipStream_t stream);
+/* mp_gate_noise_f32 with the offset read on the device: offset = pass_dev[0] * stride.  A captured decode step keys its draws on a pass
+ * counter the graph advances (mp_advance_ints): each replay draws what the host-keyed launch for that pass draws. */
+int mp_gate_noise_dev_f32(float* out, int64_t n, uint64_t seed, const int* pass_dev, uint64_t stride, int gumbel, hipStream_t stream);
 /* MOELayer dispatch / combine as index gathers (replaces einsum "sec,sm->ecm" / "sec,ecm->sm"); top_k (1 or 2) entries per
  * token in the layout above. */
 /* Post-attention RMSNorm and the MoE gate in one pass over the rows (LlamaRMSNorm + TopKGate's `logits = x.float() @ wg.float()^T`,

@@ -629,6 +629,104 @@ __global__ __launch_bounds__(256) void decode_norm_gate_route_kernel(const bf16_
     moe_route_top1_small_body(gates_sh, rts, T, E, capacity, expert, slot, weight, kept_counts, exp_counts, l_aux, nullptr, lane);
 }
 
+// ---------------- decode rows (T <= 8): post-attention RMSNorm + gate + top-2 routing in ONE launch ----------------
+// moe_route_top2_kernel's rule for a handful of tokens on one wave, lane = token.  The 1024-thread kernel gives a token's thread the
+// chunk of one token (T <= 1024), so every sum below has its order: a gate column's total is the wave butterfly of wave 0 (the other
+// waves add exact zeros), the per-expert choice totals are ballot counts, and the locations are ranks in token order.
+__device__ __forceinline__ void moe_route_top2_small_body(const float* __restrict__ gates, const float* __restrict__ logits,
+                                                          const float* __restrict__ noise, int T, int E, int capacity,
+                                                          int* __restrict__ expert, int* __restrict__ slot, float* __restrict__ weight,
+                                                          int* __restrict__ kept_counts, long long* __restrict__ exp_counts,
+                                                          float* __restrict__ l_aux, int s) {
+  const bool live = s < T;
+  int b1 = 0, b2 = -1;
+  if (live) {
+    float bv = gates[(int64_t)s * E];
+    for (int e = 1; e < E; ++e) {
+      const float g = gates[(int64_t)s * E + e];
+      if (g > bv) { bv = g; b1 = e; }
+    }
+    float b2v = -INFINITY;
+    for (int e = 0; e < E; ++e) {
+      if (e == b1) continue;
+      const float v = logits[(int64_t)s * E + e] + (noise ? noise[(int64_t)s * E + e] : 0.f);
+      if (b2 < 0 || v > b2v) { b2v = v; b2 = e; }
+    }
+    if (b2 < 0) b2 = b1;                       // E == 1: degenerate, second choice dropped below
+  }
+  const unsigned long long below = (1ull << s) - 1ull;
+  float aux = 0.f;
+  int l1 = 0, l2 = 0;
+  for (int e = 0; e < E; ++e) {
+    const float msum = wave_sum(live ? gates[(int64_t)s * E + e] : 0.f);
+    const unsigned long long m1 = __ballot(live && b1 == e), m2 = __ballot(live && E > 1 && b2 == e);
+    const int t1 = __popcll(m1), t2 = __popcll(m2);
+    aux += (msum / (float)T) * ((float)t1 / (float)T);
+    if (s == 0) { exp_counts[e] = (long long)t1 + t2; kept_counts[e] = min(capacity, t1 + t2); }
+    if (live && b1 == e) l1 = __popcll(m1 & below);
+    if (live && E > 1 && b2 == e) l2 = t1 + __popcll(m2 & below);     // second choices sit behind ALL first choices of that expert
+  }
+  if (s == 0) l_aux[0] = aux * (float)E;
+  if (!live) return;
+  const bool k1 = l1 < capacity, k2 = (E > 1) && l2 < capacity;
+  float g1 = k1 ? gates[(int64_t)s * E + b1] : 0.f;
+  float g2 = k2 ? gates[(int64_t)s * E + b2] : 0.f;
+  const float den = fmaxf(g1 + g2, 1.1920929e-07f);
+  expert[s] = b1; expert[T + s] = b2;
+  slot[s] = k1 ? l1 : -1; slot[T + s] = k2 ? l2 : -1;
+  weight[s] = g1 / den; weight[T + s] = g2 / den;
+}
+
+// The top-2 sibling of decode_norm_gate_route_kernel: the same RMSNorm (rmsnorm_bf16_kernel's 256-thread row), the gate of moe_gate_token
+// with the logits kept (the second choice ranks logits + noise), then moe_route_top2_small_body on wave 0.  Bit-identical with
+// mp_rmsnorm_bf16 + mp_moe_gate_bf16 + mp_moe_route_top2 (which cost three launches, the 1024-thread routing one ~25 us of block reductions).
+__global__ __launch_bounds__(256) void decode_norm_gate_route_top2_kernel(const bf16_t* __restrict__ x, int64_t ldx, const float* __restrict__ ln_w,
+                                                                          float eps, const float* __restrict__ wg, bf16_t* __restrict__ h,
+                                                                          int64_t ldh, const float* __restrict__ noise, int T, int d, int E,
+                                                                          int capacity, int* __restrict__ expert, int* __restrict__ slot,
+                                                                          float* __restrict__ weight, int* __restrict__ kept_counts,
+                                                                          long long* __restrict__ exp_counts, float* __restrict__ l_aux) {
+  __shared__ float red[16];
+  __shared__ float gates_sh[8 * MAXE], logits_sh[8 * MAXE];
+  constexpr int NC = 4;                                // dim <= 256 * 8 * 4
+  for (int row = 0; row < T; ++row) {
+    const bf16_t* xr = x + row * ldx;
+    bf16_t* hr = h + row * ldh;
+    bf16x8 v[NC];
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = (c * 256 + threadIdx.x) * 8;
+      if (i < d) {
+        v[c] = *reinterpret_cast<const bf16x8*>(xr + i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float f = (float)v[c][j]; ss += f * f; }
+      }
+    }
+    ss = block_sum(ss, red);
+    const float rs = rsqrtf(ss / (float)d + eps);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = (c * 256 + threadIdx.x) * 8;
+      if (i < d) {
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const bf16_t t = (bf16_t)((float)v[c][j] * rs);
+          o[j] = (bf16_t)(ln_w[i + j] * (float)t);
+        }
+        *reinterpret_cast<bf16x8*>(hr + i) = o;
+      }
+    }
+  }
+  __syncthreads();                                     // the normed rows are visible to the whole workgroup
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int row = wave; row < T; row += 4) moe_gate_token(h + row * ldh, wg, d, E, lane, logits_sh + row * E, gates_sh + row * E);
+  __syncthreads();
+  if (wave == 0)
+    moe_route_top2_small_body(gates_sh, logits_sh, noise, T, E, capacity, expert, slot, weight, kept_counts, exp_counts, l_aux, lane);
+}
+
 // DeepSpeed "residual MoE" (MoE(use_residual=True), deepspeed/moe/layer.py forward): out = x + (moe * c0 + mlp * c1) with
 // c = softmax(coefficient(h)) over two logits; bf16 rounding points of the bf16 module: the softmax result, each product, their sum,
 // the decoder layer's residual add.
@@ -824,15 +922,28 @@ __global__ __launch_bounds__(1024) void moe_route_top2_kernel(const float* __res
 // out[i] = U(0,1) (mode 0) or Gumbel(0,1) = -log(-log U) (mode 1) from a SplitMix64 hash of (seed, offset + i): stateless,
 // reproducible for a given (seed, offset), independent of the launch geometry.  DeepSpeed draws these from torch's generator
 // (sharded_moe.py: uniform_map / gumbel_rsample); the streams cannot match bit for bit, only in distribution.
-__global__ void gate_noise_kernel(float* __restrict__ out, int64_t n, unsigned long long seed, unsigned long long offset, int mode) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ float gate_noise_value(unsigned long long seed, unsigned long long offset, int64_t i, int mode) {
   unsigned long long z = seed * 0x9E3779B97F4A7C15ull + (offset + (unsigned long long)i + 1ull) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   z = z ^ (z >> 31);
   const float u = ((float)(z >> 40) + 0.5f) * (1.f / 16777216.f);      // 24 random bits, strictly inside (0, 1)
-  out[i] = mode == 1 ? -logf(-logf(u)) : u;
+  return mode == 1 ? -logf(-logf(u)) : u;
+}
+
+__global__ void gate_noise_kernel(float* __restrict__ out, int64_t n, unsigned long long seed, unsigned long long offset, int mode) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = gate_noise_value(seed, offset, i, mode);
+}
+
+// The same draws with the offset read on the device: offset = pass_dev[0] * stride.  A captured decode step keys its draws on a pass
+// counter the graph advances (mp_advance_ints), so every replay draws what the host-keyed launch of that pass would.
+__global__ void gate_noise_dev_kernel(float* __restrict__ out, int64_t n, unsigned long long seed, const int* __restrict__ pass_dev,
+                                      unsigned long long stride, int mode) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = gate_noise_value(seed, (unsigned long long)(unsigned)pass_dev[0] * stride, i, mode);
 }
 
 }  // namespace
@@ -929,6 +1040,20 @@ extern "C" int mp_decode_norm_gate_route(const void* x, int64_t ldx, const float
   return mp_check_launch("mp_decode_norm_gate_route");
 }
 
+extern "C" int mp_decode_norm_gate_route_top2(const void* x, int64_t ldx, const float* ln_w, float eps, const float* wg, void* h, int64_t ldh,
+                                              const float* noise, int tokens, int dim, int n_experts, int capacity, int* expert, int* slot,
+                                              float* weight, int* kept_counts, long long* exp_counts, float* l_aux, hipStream_t stream) {
+  MP_REQUIRE(tokens >= 1 && tokens <= 8 && n_experts >= 1 && n_experts <= MAXE && dim % 8 == 0 && dim <= 8192 && ldx % 8 == 0 &&
+                 ldh % 8 == 0 && capacity >= 0,
+             MP_ERR_SHAPE, "mp_decode_norm_gate_route_top2: tokens <= 8, experts <= %d, dim %% 8 == 0 and <= 8192 (tokens=%d experts=%d dim=%d)",
+             MAXE, tokens, n_experts, dim);
+  MP_REQUIRE(x && ln_w && wg && h && expert && slot && weight && kept_counts && exp_counts && l_aux, MP_ERR_ARG,
+             "mp_decode_norm_gate_route_top2: null operand");
+  hipLaunchKernelGGL(decode_norm_gate_route_top2_kernel, dim3(1), dim3(256), 0, stream, (const bf16_t*)x, ldx, ln_w, eps, wg, (bf16_t*)h, ldh,
+                     noise, tokens, dim, n_experts, capacity, expert, slot, weight, kept_counts, exp_counts, l_aux);
+  return mp_check_launch("mp_decode_norm_gate_route_top2");
+}
+
 extern "C" int mp_moe_residual_mix_bf16(const void* x, const void* moe, const void* mlp, const void* coef, int64_t ldcoef, void* out,
                                        int64_t tokens, int dim, hipStream_t stream) {
   MP_REQUIRE(dim % 8 == 0 && ldcoef >= 2, MP_ERR_SHAPE, "mp_moe_residual_mix_bf16: bad shape");
@@ -963,6 +1088,15 @@ extern "C" int mp_gate_noise_f32(float* out, int64_t n, uint64_t seed, uint64_t 
   hipLaunchKernelGGL(gate_noise_kernel, dim3((unsigned)mp_cdiv(n, 256)), dim3(256), 0, stream, out, n, (unsigned long long)seed,
                      (unsigned long long)offset, gumbel ? 1 : 0);
   return mp_check_launch("mp_gate_noise_f32");
+}
+
+extern "C" int mp_gate_noise_dev_f32(float* out, int64_t n, uint64_t seed, const int* pass_dev, uint64_t stride, int gumbel, hipStream_t stream) {
+  MP_REQUIRE(n >= 0, MP_ERR_SHAPE, "mp_gate_noise_dev_f32: bad size");
+  MP_REQUIRE(pass_dev != nullptr, MP_ERR_ARG, "mp_gate_noise_dev_f32: pass_dev is null");
+  if (n == 0) return MP_OK;
+  hipLaunchKernelGGL(gate_noise_dev_kernel, dim3((unsigned)mp_cdiv(n, 256)), dim3(256), 0, stream, out, n, (unsigned long long)seed, pass_dev,
+                     (unsigned long long)stride, gumbel ? 1 : 0);
+  return mp_check_launch("mp_gate_noise_dev_f32");
 }
 
 extern "C" int mp_moe_dispatch_bf16(const void* x, int64_t ldx, const int* expert, const int* slot, void* buf, int64_t ldbuf, int64_t tokens, int dim,

@@ -139,6 +139,45 @@ __global__ __launch_bounds__(256) void gemv_shared_kernel(GemvArgs g) {
   }
 }
 
+// One row of the indexed (expert) form: the wave's four W rows against x row xr, four 512-element steps per trip (16 weight loads in
+// flight per lane: one step per trip left every trip waiting on its own 4 loads — the down projection's 21.5 trips per row were 21.5
+// dependent round trips), then the wave reduction.  acc[r] = x . W[row r].
+__device__ __forceinline__ void gv_indexed_row_dot(const bf16_t* __restrict__ xr, const bf16_t* const (&wp)[4], int K, int lane, float (&acc)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] = 0.f;
+  int k = lane * 8;
+  for (; k + 3 * 512 < K; k += 4 * 512) {
+    bf16x8 xs[4], ws[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      xs[u] = *reinterpret_cast<const bf16x8*>(xr + k + u * 512);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ws[u][r] = gv_ldw(wp[r] + k + u * 512);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(xs[u], ws[u][r], acc[r]);
+  }
+  for (; k < K; k += 512) {
+    const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(xr + k);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(x0, gv_ldw(wp[r] + k), acc[r]);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] = wave_sum(acc[r]);
+}
+
+// The indexed form's SwiGLU epilogue (lane 0): gate rows {g0, g0+1} and their up rows {g0+32, g0+33} -> two output columns.
+__device__ __forceinline__ void gv_swiglu_store(const float (&acc)[4], const int (&rows)[4], int N, bf16_t* __restrict__ yo) {
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const float gf = (float)(bf16_t)acc[p], uf = (float)(bf16_t)acc[2 + p];
+    const int col = (rows[p] >> 6) * 32 + (rows[p] & 31);
+    if (rows[p] < N) yo[col] = (bf16_t)(gf * mp_sigmoid_fast(gf) * uf);
+  }
+}
+
 // INDEXED: every row picks its own weight matrix (MoE experts); rows are processed one after the other
 template <bool SWIGLU>
 __global__ __launch_bounds__(256) void gemv_indexed_kernel(GemvArgs g) {
@@ -161,39 +200,12 @@ __global__ __launch_bounds__(256) void gemv_indexed_kernel(GemvArgs g) {
     const bf16_t* wp[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(rows[r], g.N - 1) * g.ldw;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    int k = lane * 8;
-    // four steps per trip: 16 weight loads in flight per lane (one step per trip left every trip waiting on its own 4 loads: the down
-    // projection's 21.5 trips per row were 21.5 dependent round trips); same accumulation order
-    for (; k + 3 * 512 < g.K; k += 4 * 512) {
-      bf16x8 xs[4], ws[4][4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        xs[u] = *reinterpret_cast<const bf16x8*>(g.x + (int64_t)m * g.ldx + k + u * 512);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ws[u][r] = gv_ldw(wp[r] + k + u * 512);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(xs[u], ws[u][r], acc[r]);
-    }
-    for (; k < g.K; k += 512) {
-      const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(g.x + (int64_t)m * g.ldx + k);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(x0, gv_ldw(wp[r] + k), acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = wave_sum(acc[r]);
+    float acc[4];
+    gv_indexed_row_dot(g.x + (int64_t)m * g.ldx, wp, g.K, lane, acc);
     if (lane != 0) continue;
     bf16_t* yo = reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy;
     if (SWIGLU) {
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const float gf = (float)(bf16_t)acc[p], uf = (float)(bf16_t)acc[2 + p];
-        const int col = (rows[p] >> 6) * 32 + (rows[p] & 31);
-        if (rows[p] < g.N) yo[col] = (bf16_t)(gf * mp_sigmoid_fast(gf) * uf);
-      }
+      gv_swiglu_store(acc, rows, g.N, yo);
     } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -516,6 +528,30 @@ __global__ __launch_bounds__(256) void gemv_rmsnorm_rope_kernel(GemvArgs g, cons
 // form's 18.8 on the 90 MB down projection, bit-identical.  A launch here is ~4 us of fixed cost (dispatch, first latency, reduction,
 // epilogue) + bytes / 6.3 TB/s — qkv 16.0 + 3.3, o 5.3 + 3.9, gate|up 28.6 + 1.9, down 14.3 + 4.5 (profiles/r05a_decode_timeline_dense.md) —
 // and the eight loads per lane it keeps in flight already cover the latency; deeper queues only lengthen the register-file fill.
+// K part kp (0..3) of one row in the K-split form: the 512-element steps s = kp, kp + 4, ... against the wave's four W rows, two of
+// them per trip (8 weight loads in flight per lane), then the wave reduction.  acc[r] = this part's share of x . W[row r].
+__device__ __forceinline__ void gv_ksplit_part_dot(const bf16_t* __restrict__ xr, const bf16_t* const (&wp)[4], int K, int lane, int kp,
+                                                   float (&acc)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] = 0.f;
+  int k = lane * 8 + kp * 512;
+  for (; k + 2048 < K; k += 4096) {
+    const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(xr + k), x1 = *reinterpret_cast<const bf16x8*>(xr + k + 2048);
+    bf16x8 w0[4], w1[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { w0[r] = gv_ldw(wp[r] + k); w1[r] = gv_ldw(wp[r] + k + 2048); }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(x1, w1[r], gv_dot8(x0, w0[r], acc[r]));
+  }
+  if (k < K) {
+    const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(xr + k);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(x0, gv_ldw(wp[r] + k), acc[r]);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] = wave_sum(acc[r]);
+}
+
 __global__ __launch_bounds__(1024) void gemv_ksplit_kernel(GemvArgs g) {
   __shared__ float red[4][4][4];                            // [kp][rg][r]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -526,24 +562,8 @@ __global__ __launch_bounds__(1024) void gemv_ksplit_kernel(GemvArgs g) {
     const bf16_t* wp[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(row0 + r, g.N - 1) * g.ldw;
-    const bf16_t* xr = g.x + (int64_t)m * g.ldx;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    int k = lane * 8 + kp * 512;
-    for (; k + 2048 < g.K; k += 4096) {                     // two of this wave's steps per trip: 8 weight loads in flight per lane
-      const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(xr + k), x1 = *reinterpret_cast<const bf16x8*>(xr + k + 2048);
-      bf16x8 w0[4], w1[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { w0[r] = gv_ldw(wp[r] + k); w1[r] = gv_ldw(wp[r] + k + 2048); }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(x1, w1[r], gv_dot8(x0, w0[r], acc[r]));
-    }
-    if (k < g.K) {
-      const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(xr + k);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(x0, gv_ldw(wp[r] + k), acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = wave_sum(acc[r]);
+    float acc[4];
+    gv_ksplit_part_dot(g.x + (int64_t)m * g.ldx, wp, g.K, lane, kp, acc);
     if (m > 0) __syncthreads();                             // the previous row's partials have been read
     if (lane == 0) {
 #pragma unroll
@@ -571,6 +591,71 @@ __global__ __launch_bounds__(1024) void gemv_ksplit_kernel(GemvArgs g) {
         reinterpret_cast<bf16_t*>(g.y)[(int64_t)m * g.ldy + n] = (bf16_t)v;
       }
     }
+  }
+}
+
+// ---------------- top-2 MoE decode: the two expert GEMVs of 2T (token, choice) entries ----------------
+// Entry layout of mp_moe_route_top2: entry e = c * T + t is choice c (0 = first, 1 = second) of token t, with expert index w_index[e],
+// slot row_keep[e] (< 0: dropped by the capacity limit) and combine weight row_scale[e].
+// gate|up: act[e] = SwiGLU(x[t] . W[w_index[e]]) — gemv_indexed_kernel<true>'s arithmetic per entry, x row e % T.  A dropped entry
+// streams no weights and its act row is not written (the down projection never reads it).
+__global__ __launch_bounds__(256) void gemv_top2_gate_up_kernel(GemvArgs g, int T) {
+  const int lane = threadIdx.x & 63;
+  const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int pair = wid * 2;
+  const int blk = pair >> 5, j = pair & 31;
+  const int rows[4] = {blk * 64 + j, blk * 64 + j + 1, blk * 64 + j + 32, blk * 64 + j + 33};
+  if (rows[0] >= g.N) return;
+  for (int e = 0; e < 2 * T; ++e) {
+    if (g.row_keep[e] < 0) continue;
+    const bf16_t* Wm = g.W + (int64_t)g.w_index[e] * g.strideW;
+    const bf16_t* wp[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(rows[r], g.N - 1) * g.ldw;
+    float acc[4];
+    gv_indexed_row_dot(g.x + (int64_t)(e % T) * g.ldx, wp, g.K, lane, acc);
+    if (lane == 0) gv_swiglu_store(acc, rows, g.N, reinterpret_cast<bf16_t*>(g.y) + (int64_t)e * g.ldy);
+  }
+}
+
+// down + combine: y[t, n] = bf16(residual[t, n] + acc), acc = 0 then acc = fma(w_c, bf16(act[c*T + t] . W[w_index[c*T + t]][n]), acc) for
+// the kept choices c = 0, 1 in that order — mp_moe_combine_bf16's summation order and rounding points, on expert outputs computed as
+// gemv_ksplit_kernel computes them (sixteen waves per sixteen rows, K split four ways, the parts added in ascending order).  One launch.
+__global__ __launch_bounds__(1024) void gemv_top2_down_kernel(GemvArgs g, int T) {
+  __shared__ float red[4][4][4];                            // [kp][rg][r]
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int rg = wv & 3, kp = wv >> 2;
+  const int row0 = (blockIdx.x * 4 + rg) * 4;
+  const int n = row0 + lane;                                // (lane r of the kp = 0 wave finishes row r of its group)
+  const bool fin = kp == 0 && lane < 4 && n < g.N;
+  for (int t = 0; t < T; ++t) {
+    float y[2] = {0.f, 0.f};
+    for (int c = 0; c < 2; ++c) {
+      const int e = c * T + t;
+      if (g.row_keep[e] < 0) continue;                      // (uniform over the workgroup)
+      const bf16_t* Wm = g.W + (int64_t)g.w_index[e] * g.strideW;
+      const bf16_t* wp[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(row0 + r, g.N - 1) * g.ldw;
+      float acc[4];
+      gv_ksplit_part_dot(g.x + (int64_t)e * g.ldx, wp, g.K, lane, kp, acc);
+      __syncthreads();                                      // the previous entry's partials have been read
+      if (lane == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[kp][rg][r] = acc[r];
+      }
+      __syncthreads();
+      if (fin) y[c] = (float)(bf16_t)(((red[0][rg][lane] + red[1][rg][lane]) + red[2][rg][lane]) + red[3][rg][lane]);
+    }
+    if (!fin) continue;
+    float acc = 0.f;
+    for (int c = 0; c < 2; ++c) {
+      const int e = c * T + t;
+      if (g.row_keep[e] < 0) continue;
+      acc = fmaf(g.row_scale[e], y[c], acc);
+    }
+    bf16_t* yo = reinterpret_cast<bf16_t*>(g.y) + (int64_t)t * g.ldy;
+    yo[n] = g.residual ? (bf16_t)((float)g.residual[(int64_t)t * g.ldr + n] + acc) : (bf16_t)acc;
   }
 }
 
@@ -624,6 +709,31 @@ extern "C" int mp_gemv_bf16(const void* x, int64_t ldx, const void* W, int64_t l
     }
   }
   return mp_check_launch("mp_gemv_bf16");
+}
+
+extern "C" int mp_gemv_top2_gate_up_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* act, int64_t ldact,
+                                         const int* expert, const int* slot, int tokens, int N, int K, hipStream_t stream) {
+  MP_REQUIRE(tokens >= 1 && tokens <= GV_MAXM && N > 0 && N % 64 == 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 &&
+                 strideW % 8 == 0 && ldact >= N / 2, MP_ERR_SHAPE,
+             "mp_gemv_top2_gate_up_bf16: 1 <= tokens <= 8, N %% 64 == 0, K %% 8 == 0 (tokens=%d N=%d K=%d)", tokens, N, K);
+  MP_REQUIRE(x && W && act && expert && slot, MP_ERR_ARG, "mp_gemv_top2_gate_up_bf16: null operand");
+  GemvArgs g{(const bf16_t*)x, ldx, (const bf16_t*)W, ldw, strideW, act, ldact, nullptr, nullptr, 0, expert, nullptr, slot, 2 * tokens, N, K,
+             ACT_SWIGLU_PAIR, 0, 1.f};
+  hipLaunchKernelGGL(gemv_top2_gate_up_kernel, dim3((unsigned)mp_cdiv(N / 4, 4)), dim3(256), 0, stream, g, tokens);
+  return mp_check_launch("mp_gemv_top2_gate_up_bf16");
+}
+
+extern "C" int mp_gemv_top2_down_bf16(const void* act, int64_t ldact, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy,
+                                      const void* residual, int64_t ldr, const int* expert, const int* slot, const float* weight, int tokens,
+                                      int N, int K, hipStream_t stream) {
+  MP_REQUIRE(tokens >= 1 && tokens <= GV_MAXM && N > 0 && K > 0 && K % 8 == 0 && ldact % 8 == 0 && ldw % 8 == 0 && strideW % 8 == 0 &&
+                 ldy >= N && (!residual || ldr >= N), MP_ERR_SHAPE,
+             "mp_gemv_top2_down_bf16: 1 <= tokens <= 8, K %% 8 == 0 (tokens=%d N=%d K=%d)", tokens, N, K);
+  MP_REQUIRE(act && W && y && expert && slot && weight, MP_ERR_ARG, "mp_gemv_top2_down_bf16: null operand");
+  GemvArgs g{(const bf16_t*)act, ldact, (const bf16_t*)W, ldw, strideW, y, ldy, nullptr, (const bf16_t*)residual, ldr, expert, weight, slot,
+             2 * tokens, N, K, ACT_NONE, 0, 1.f};
+  hipLaunchKernelGGL(gemv_top2_down_kernel, dim3((unsigned)mp_cdiv(mp_cdiv(N, 4), 4)), dim3(1024), 0, stream, g, tokens);
+  return mp_check_launch("mp_gemv_top2_down_bf16");
 }
 
 extern "C" int mp_gemv_rmsnorm_bf16(const void* x, int64_t ldx, const float* norm_w, float eps, const void* W, int64_t ldw, void* y,

@@ -54,6 +54,7 @@ class LlamaStack:
         self.training = True
         self.rts_uniform_provider = None   # callable(layer_idx, T, E) -> fp32 [T,E] gate draws (RTS uniforms / top-2 Gumbel) or None
         self.gate_pass = 0                 # forward passes so far: part of the key of the stateless gate-draw generator
+        self._pass_dev = None              # int32 [1] on the device: the pass number of the decode step being captured (decode_step)
         self.ep = None                     # ExpertParallel (expert_parallel.py) once enable_expert_parallel() sharded the experts
         self.fuse_moe_gather_scatter = True   # top-1, one rank: dispatch / combine folded into the expert GEMMs
         self.fuse_decode_routing = True       # decode rows: post-attention norm + gate + routing in one launch
@@ -177,9 +178,13 @@ class LlamaStack:
         # the generator is keyed by (seed, offset + index) and a pass's layers occupy consecutive offsets: ONE launch per forward pass draws
         # for all layers (the same numbers as a launch per layer, which sat between every layer's routing kernel and its expert GEMMs)
         L = len(self.layers)
-        key = (self.gate_pass, T, E, bool(gumbel))
+        pass_dev = self._pass_dev
+        key = (self.gate_pass, T, E, bool(gumbel), pass_dev is not None)
         if getattr(self, "_draws_key", None) != key:
-            self._draws_all = ops.gate_noise(L * T * E, self.cfg.moe_gate_seed, self.gate_pass * L * T * E, gumbel, self.device)
+            if pass_dev is not None:       # a decode step under a HIP graph: the pass number is read on the device (decode_step)
+                self._draws_all = ops.gate_noise_dev(L * T * E, self.cfg.moe_gate_seed, pass_dev, L * T * E, gumbel, self.device)
+            else:
+                self._draws_all = ops.gate_noise(L * T * E, self.cfg.moe_gate_seed, self.gate_pass * L * T * E, gumbel, self.device)
             self._draws_key = key
         return self._draws_all[i * T * E:(i + 1) * T * E]
 
@@ -207,6 +212,13 @@ class LlamaStack:
             act = ops.gemv(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR, w_index=expert)
             out = ops.gemv(act, lw["down"], residual=x, w_index=expert, row_scale=weight, row_keep=slot)
             return out, l_aux, (expert, slot, counts)
+        if k == 2 and self.ep is None and T <= 8 and not cfg.use_residual:
+            # decode rows, top-2: the 2T (token, choice) entries stream their experts' matrices (GEMVs with a device-side expert index);
+            # the down projection adds both weighted expert outputs and the residual in moe_combine's order (decode_step's fused form
+            # takes the same two launches behind its one-launch routing)
+            expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2(gates, logits, cap, self._gate_draws(i, T, E, gumbel=True))
+            act = ops.gemv_top2_gate_up(h, lw["gu"], expert, slot)
+            return ops.gemv_top2_down(act, lw["down"], expert, slot, weight, x), l_aux, (expert, slot, counts)
         if k == 1 and self.ep is None and self.fuse_moe_gather_scatter and not cfg.use_residual:
             # top-1 on one rank: the dispatch is a row gather in the gate|up GEMM's operand fetch and the combine (gate weight and
             # the layer's residual add) a row scatter in the down GEMM's epilogue; every routed token's row is written exactly once,
@@ -368,7 +380,7 @@ class LlamaStack:
             self.last_gate_inputs = gate_inputs            # per MoE layer: the residual stream in front of the post-attention norm (oracle/parity.py)
         return out.view(B, S, d), aux, (routing if collect_routing else None)
 
-    def decode_step(self, emb, kv_cache, counters):
+    def decode_step(self, emb, kv_cache, counters, pass_dev=None):
         """One token per sequence against the KV cache with the cache length held ON THE DEVICE (`counters` int32 [2] =
         [position of the new token, number of valid keys after appending it]): no launch argument depends on the step, so the
         whole step can be captured once into a HIP graph and replayed per token (evaluate()).  emb [B, 1, d] -> hidden [B, 1, d].
@@ -376,7 +388,17 @@ class LlamaStack:
         Reproducibility note (round-4 advisor): the narrow projections (o_proj, down) take the K-split GEMV when B == 1 or an expert index is
         given and the shared-weight form otherwise; the two add their partial dot products in different orders, so the SAME prompt decoded at
         batch 1 and at batch 2 may differ in the last fp32 bit of those projections (and, at a near-tie of two logits, in a greedy token).
-        Within one batch size every step is bit-reproducible; MP_GEMV_KSPLIT=0 selects the shared form for every batch size."""
+        Within one batch size every step is bit-reproducible; MP_GEMV_KSPLIT=0 selects the shared form for every batch size.
+        pass_dev (int32 [1] on the device, or None): the number of this forward pass, read on the device by the gate's random draws
+        (moe_gate_sampling) instead of the host counter `gate_pass` — a captured step then draws, at every replay, what the token-by-token
+        loop draws for that pass; the caller advances it with the counters."""
+        self._pass_dev = pass_dev
+        try:
+            return self._decode_step(emb, kv_cache, counters)
+        finally:
+            self._pass_dev = None
+
+    def _decode_step(self, emb, kv_cache, counters):
         cfg = self.cfg
         B, _, d = emb.shape
         H, D = cfg.num_attention_heads, cfg.head_dim
@@ -401,6 +423,14 @@ class LlamaStack:
                 h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
                 act = ops.gemv(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR, w_index=expert)
                 x = ops.gemv(act, lw["down"], residual=x, w_index=expert, row_scale=weight, row_keep=slot)
+            elif (i in self.moe_layers and cfg.top_k_experts == 2 and self.ep is None and B <= 8 and self.fuse_decode_routing
+                    and not cfg.use_residual):
+                # top-2: norm + gate + routing in one launch, then the two-expert GEMVs (the bits of _mlp's decode-row top-2 branch)
+                E, cap = cfg.num_experts, self.capacity(B)
+                h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route_top2(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap,
+                                                                                   self._gate_draws(i, B, E, gumbel=True))
+                act = ops.gemv_top2_gate_up(h, lw["gu"], expert, slot)
+                x = ops.gemv_top2_down(act, lw["down"], expert, slot, weight, x)
             elif fold and i not in self.moe_layers:
                 # dense layer: post_attention_layernorm inside the gate|up GEMV (same bits as rmsnorm + gemv), then the down projection
                 act = ops.gemv_rmsnorm(x, lw["ln2"], cfg.rms_norm_eps, lw["gu"], act=ops.ACT_SWIGLU_PAIR)

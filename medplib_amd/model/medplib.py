@@ -165,6 +165,7 @@ class MedPLIBForCausalLM(nn.Module):
         # model_forward returns (the loss dict is safe to read); backward and optimizer stay asynchronous to it and are ordered
         # against the next tail by the tail stream itself.  Anything else that touches trainable state calls sync_side_streams().
         self.decode_with_graph = True            # evaluate(): replay one captured HIP graph per generated token
+        self.last_decode_path = None             # "graph" or "loop": how the last generate() / evaluate() decoded
         self.tail_side_stream = False
         self._tail_stream_obj = None
         self.active_tail_stream = None
@@ -719,13 +720,18 @@ class MedPLIBForCausalLM(nn.Module):
         hid_all = torch.empty((max_new_tokens, d), dtype=torch.bfloat16, device=dev)
         toks[0:1].copy_(tok)
         h_static = torch.empty((1, 1, d), dtype=torch.bfloat16, device=dev)
+        # the gate's random draws (moe_gate_sampling) are keyed on the forward-pass number: the token-by-token loop gives the decode step
+        # of token i pass pass0 + i, so the graph reads it from a device counter it advances itself
+        pass0 = llm.gate_pass
+        pass_dev = torch.tensor([pass0 + 1], dtype=torch.int32, device=dev)
 
         def step():
             emb = ops.splice_rows(llm.embed_tokens, None, tok, d)
-            h = llm.decode_step(emb.view(1, 1, d), cache, counters)
+            h = llm.decode_step(emb.view(1, 1, d), cache, counters, pass_dev=pass_dev)
             h_static.copy_(h)
             tok.copy_(ops.argmax_rows(llm.next_token_logits(h[0, -1:])))
             ops.advance_ints(counters, 1)
+            ops.advance_ints(pass_dev, 1)
 
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
@@ -748,7 +754,17 @@ class MedPLIBForCausalLM(nn.Module):
                 done = True
         generated = toks[:n].cpu().tolist()
         step_hiddens = [hid_all[i:i + 1].view(1, 1, d) for i in range(n - 1)]
+        llm.gate_pass = pass0 + n - 1            # the passes the loop would have made (replays past the first EOS are discarded)
+        llm._draws_key = None                    # (the captured draw buffer belongs to the graph)
         return generated, step_hiddens
+
+    def _graph_decode_ok(self):
+        """Whether _decode_graph computes what the token-by-token loop computes for this model: top-1, or top-2 on one rank without the
+        residual MoE and without injected gate draws (a host-side provider would be frozen into the graph)."""
+        cfg, llm = self.config, self.model.llm
+        if cfg.top_k_experts == 1:
+            return True
+        return cfg.top_k_experts == 2 and llm.ep is None and not cfg.use_residual and llm.rts_uniform_provider is None
 
     def _greedy(self, ids, images_clip, max_new_tokens, eos_token_id, mask_images=None, image_token_types=None, image_token_lengths=None,
                 region_masks=None, valid_region_masks_bool=None):
@@ -764,9 +780,11 @@ class MedPLIBForCausalLM(nn.Module):
         embeds = ops.splice_rows(m.llm.embed_tokens, feats, src, cfg.hidden_size).view(1, S, cfg.hidden_size)
         cache = m.llm.new_kv_cache(1, S + max_new_tokens)
         hidden, _, _ = m.llm.forward(embeds, None, kv_cache=cache)
-        if self.decode_with_graph and max_new_tokens > 2 and cfg.top_k_experts == 1:
+        if self.decode_with_graph and max_new_tokens > 2 and self._graph_decode_ok():
+            self.last_decode_path = "graph"
             generated, step_hiddens = self._decode_graph(hidden, cache, S, max_new_tokens, eos_token_id)
         else:
+            self.last_decode_path = "loop"
             generated, step_hiddens = [], []
             last = hidden[0, -1:]
             for _ in range(max_new_tokens):

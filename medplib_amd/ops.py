@@ -1480,6 +1480,64 @@ def decode_norm_gate_route(x, ln_w, eps, wg, capacity, rts_uniform=None):
     return h, expert, slot, weight, kept, counts, l_aux
 
 
+def decode_norm_gate_route_top2(x, ln_w, eps, wg, capacity, noise=None):
+    """Decode rows (T <= 8): post-attention RMSNorm + gate + top-2 routing in one launch (bit-identical with rmsnorm + moe_gate +
+    moe_route_top2).  noise: fp32 [T, E] Gumbel draws of the second choice or None.
+    -> (h [T, d] bf16, expert, slot, weight [2T] in moe_route_top2's entry layout, kept [E], counts [E], l_aux [1])."""
+    _chk(x, torch.bfloat16, "decode_norm_gate_route_top2.x"); _chk(ln_w, torch.float32, "decode_norm_gate_route_top2.ln_w")
+    _chk(wg, torch.float32, "decode_norm_gate_route_top2.wg")
+    T, d = x.shape
+    E = wg.shape[0]
+    assert x.stride(1) == 1 and wg.is_contiguous() and wg.shape[1] == d and ln_w.numel() == d
+    if noise is not None:
+        _chk(noise, torch.float32, "decode_norm_gate_route_top2.noise"); assert noise.is_contiguous() and noise.numel() == T * E
+    dev = x.device
+    h = torch.empty((T, d), dtype=torch.bfloat16, device=dev)
+    expert = torch.empty(2 * T, dtype=torch.int32, device=dev); slot = torch.empty(2 * T, dtype=torch.int32, device=dev)
+    weight = torch.empty(2 * T, dtype=torch.float32, device=dev)
+    kept = torch.empty(E, dtype=torch.int32, device=dev); counts = torch.empty(E, dtype=torch.int64, device=dev)
+    l_aux = torch.empty(1, dtype=torch.float32, device=dev)
+    lib().call("mp_decode_norm_gate_route_top2", _p(x), x.stride(0), _p(ln_w), float(eps), _p(wg), _p(h), h.stride(0), _p(noise), T, d, E,
+               int(capacity), _p(expert), _p(slot), _p(weight), _p(kept), _p(counts), _p(l_aux), _stream())
+    return h, expert, slot, weight, kept, counts, l_aux
+
+
+def _chk_top2_entries(T, expert, slot, weight=None):
+    _chk(expert, torch.int32, "top2.expert"); _chk(slot, torch.int32, "top2.slot")
+    assert expert.is_contiguous() and slot.is_contiguous() and expert.numel() == 2 * T and slot.numel() == 2 * T
+    if weight is not None:
+        _chk(weight, torch.float32, "top2.weight"); assert weight.is_contiguous() and weight.numel() == 2 * T
+
+
+def gemv_top2_gate_up(h, w, expert, slot):
+    """Top-2 decode rows: act[c*T + t] = SwiGLU-paired h[t] . w[expert[c*T + t]] for the 2T entries of moe_route_top2's layout; w [E, 2ff, d]
+    (interleaved gate|up rows).  Entries with slot < 0 (dropped) are skipped: their rows of act [2T, ff] are left unwritten."""
+    _chk(h, torch.bfloat16, "gemv_top2_gate_up.h"); _chk(w, torch.bfloat16, "gemv_top2_gate_up.w")
+    T, K = h.shape
+    E, N, Kw = w.shape
+    assert Kw == K and h.stride(1) == 1 and w.stride(2) == 1
+    _chk_top2_entries(T, expert, slot)
+    act = torch.empty((2 * T, N // 2), dtype=torch.bfloat16, device=h.device)
+    lib().call("mp_gemv_top2_gate_up_bf16", _p(h), h.stride(0), _p(w), w.stride(1), w.stride(0), _p(act), act.stride(0), _p(expert), _p(slot),
+               T, N, K, _stream())
+    return act
+
+
+def gemv_top2_down(act, w, expert, slot, weight, residual):
+    """Top-2 decode rows: out[t] = residual[t] + sum over the kept choices c (in order) of weight[c*T + t] * bf16(act[c*T + t] . w[expert[c*T + t]])
+    — moe_combine's order and rounding points; act [2T, ff], w [E, d, ff], residual [T, d] -> out [T, d] bf16."""
+    _chk(act, torch.bfloat16, "gemv_top2_down.act"); _chk(w, torch.bfloat16, "gemv_top2_down.w"); _chk(residual, torch.bfloat16, "gemv_top2_down.residual")
+    T2, K = act.shape
+    T = T2 // 2
+    E, N, Kw = w.shape
+    assert T2 == 2 * T and Kw == K and act.stride(1) == 1 and w.stride(2) == 1 and residual.shape == (T, N) and residual.stride(1) == 1
+    _chk_top2_entries(T, expert, slot, weight)
+    out = torch.empty((T, N), dtype=torch.bfloat16, device=act.device)
+    lib().call("mp_gemv_top2_down_bf16", _p(act), act.stride(0), _p(w), w.stride(1), w.stride(0), _p(out), out.stride(0), _p(residual),
+               residual.stride(0), _p(expert), _p(slot), _p(weight), T, N, K, _stream())
+    return out
+
+
 def gather_rows_bf16(src, idx, out=None):
     """out[r] = src[idx[r]]: bf16 rows (src any row stride), idx int64 on the device."""
     _chk(src, torch.bfloat16, "gather_rows_bf16.src")
@@ -1554,6 +1612,14 @@ def moe_route_top2(gates, logits, capacity, noise=None):
 def gate_noise(n, seed, offset, gumbel, device):
     out = torch.empty(n, dtype=torch.float32, device=device)
     lib().call("mp_gate_noise_f32", _p(out), n, int(seed), int(offset), 1 if gumbel else 0, _stream())
+    return out
+
+
+def gate_noise_dev(n, seed, pass_dev, stride, gumbel, device):
+    """gate_noise with offset = pass_dev[0] * stride read on the device (pass_dev int32 [1]): what gate_noise(n, seed, pass * stride, gumbel) draws."""
+    _chk(pass_dev, torch.int32, "gate_noise_dev.pass_dev")
+    out = torch.empty(n, dtype=torch.float32, device=device)
+    lib().call("mp_gate_noise_dev_f32", _p(out), n, int(seed), _p(pass_dev), int(stride), 1 if gumbel else 0, _stream())
     return out
 
 
