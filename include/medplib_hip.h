@@ -589,6 +589,31 @@ int mp_image_table_pad_chw(const void* src, int h, int w, int C, const float* ta
 int mp_overlay_mask_u8(const void* img, const void* mask, void* out, int64_t n_pixels, float tint_r, float tint_g, float tint_b,
                        hipStream_t stream);
 
+/* ---- retrieval of in-context examples (model/rag/image_rag.py: `build` embeds candidates, `augment` takes their top-k) --------- */
+/* Pillow's window bounds + 22-bit fixed-point coefficients of one axis for a filter id: 2 = BILINEAR, 3 = BICUBIC (a = -0.5,
+ * support 2, widened by the scale on a downscale), i.e. the resize of CLIPImageProcessor.  HOST function; other ids return
+ * MP_ERR_ARG and ksize 0.  Applied on the device by mp_resample_axis_u8 (any ksize). */
+int mp_pil_resample_ksize(int filter, int in_size, int out_size);
+int mp_pil_resample_coeffs(int filter, int in_size, int out_size, int* bounds, int* coefs, int ksize);
+/* uint8 HWC [h, w, C] -> float / bf16 CHW [C, crop_h, crop_w]: dst[c, y, x] = table[c][src[top + y, left + x, c]] (centre crop +
+ * CLIPImageProcessor rescale / normalise through the 256-entry table). */
+int mp_image_table_crop_chw(const void* src, int h, int w, int C, const float* table, void* dst, int crop_h, int crop_w, int top,
+                            int left, int out_dtype, hipStream_t stream);
+/* Exact fp32 inner-product top-k: for each query q, scores[q, 0..k) / idx[q, 0..k) are the k largest <index[n], queries[q]> over
+ * n < N, in descending score, ties to the lower index; k > N leaves (-inf, -1) after the N real entries.  f32 in, f32 accumulate
+ * (Q > 1 on v_mfma_f32_32x32x2_f32, Q == 1 as a streaming GEMV): each score is an fp32 fma chain over C, no reduced precision.
+ * index [N, ld_index] f32 (row stride ld_index >= C, a multiple of 4), queries [Q, C] f32 contiguous, both 16-byte aligned.
+ * Limits: 1 <= k <= 64, C % 4 == 0, 1 <= N < 2^31.  workspace: mp_dot_topk_workspace_bytes(N, Q, C, k) bytes (partial lists of
+ * the workgroups; the [Q, N] score matrix is never written); -1 for shapes beyond the limits. */
+int64_t mp_dot_topk_workspace_bytes(int64_t N, int64_t Q, int C, int k);
+int mp_dot_topk_f32(const float* index, int64_t ld_index, const float* queries, int64_t N, int64_t Q, int C, int k, float* scores,
+                    int* idx, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+/* The image embedding of image_rag.py's encoder: hidden = last_hidden_state [n * S, C] bf16 (CLS first) -> out [n, C] f32,
+ * m = bf16(mean over rows 1..S-1, fp32 sum), out = m / (||m||_2 + 1e-12). */
+int mp_clip_pool_normalize_bf16(const void* hidden, int n, int S, int C, float* out, hipStream_t stream);
+/* out[r] = x[r] / (||x[r]||_2 + 1e-12), rows [rows, C] f32 (in place allowed): load_index's normalisation of the stored rows. */
+int mp_l2_normalize_rows_f32(const float* x, float* out, int64_t rows, int C, hipStream_t stream);
+
 /* ---- optimizer (train_ds_medplib.py:383-420: AdamW betas (0.9,0.95), wd 0, clip 1.0) ------------------------------ */
 /* out_accum[0] += sum(x^2); out_accum must hold 1 + 256 floats (out_accum[1..256] = per-block partials, summed in index order: the
  * result is bit-reproducible). */

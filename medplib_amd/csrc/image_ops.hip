@@ -10,6 +10,9 @@
 //                             normalize_coeffs_8bpc); pure C double arithmetic so the values are Pillow's, bit for bit
 //   mp_resample_axis_u8       one pass over a [outer, len, inner] uint8 array (horizontal: outer = H, inner = C; vertical:
 //                             outer = 1, inner = W*C)
+//   mp_pil_resample_coeffs    host: the same for a Pillow filter id (2 = BILINEAR, 3 = BICUBIC with a = -0.5, support 2): the
+//                             resize of CLIPImageProcessor (retrieval of in-context examples, medplib_amd/rag.py)
+//   mp_image_table_crop_chw   uint8 HWC -> float / bf16 CHW through the value table, centre crop (CLIPImageProcessor crop_size)
 //   mp_image_table_pad_chw    uint8 HWC -> float / bf16 CHW through a per-channel 256-entry value table (the host fills it in the
 //                             reference's own op order: SAM `(x - pixel_mean) / pixel_std` :484, CLIP rescale + normalise) with
 //                             the centre padding of pad_tensor_channelwise (:446-477) folded in
@@ -85,6 +88,30 @@ __global__ void image_table_pad_chw_kernel(const uint8_t* __restrict__ src, int 
   dst[idx] = (TOUT)v;
 }
 
+template <typename TOUT>
+__global__ void image_table_crop_chw_kernel(const uint8_t* __restrict__ src, int w, int C, const float* __restrict__ table,
+                                            TOUT* __restrict__ dst, int crop_h, int crop_w, int top, int left) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t total = (int64_t)C * crop_h * crop_w;
+  if (idx >= total) return;
+  const int x = (int)(idx % crop_w), y = (int)((idx / crop_w) % crop_h), c = (int)(idx / ((int64_t)crop_w * crop_h));
+  dst[idx] = (TOUT)table[c * 256 + src[((int64_t)(y + top) * w + (x + left)) * C + c]];
+}
+
+// Pillow's filters (src/libImaging/Resample.c): support and weight function
+double pil_filter_support(int filter) { return filter == 3 ? 2.0 : 1.0; }
+
+double pil_filter_weight(int filter, double x) {
+  if (x < 0.0) x = -x;
+  if (filter == 3) {                                         // bicubic, a = -0.5
+    const double a = -0.5;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+  }
+  return x < 1.0 ? 1.0 - x : 0.0;                            // bilinear
+}
+
 }  // namespace
 
 // ICL overlay mode (ICLLazySupervisedDataset._overlay_mask, :46-50): where the example's mask is set, pixel = trunc(clip(pixel * 0.45f +
@@ -151,6 +178,52 @@ extern "C" int mp_pil_bilinear_coeffs(int in_size, int out_size, int* bounds, in
   return MP_OK;
 }
 
+extern "C" int mp_pil_resample_ksize(int filter, int in_size, int out_size) {
+  if ((filter != 2 && filter != 3) || in_size <= 0 || out_size <= 0) return 0;
+  double filterscale = (double)((float)in_size - 0.0f) / out_size;
+  if (filterscale < 1.0) filterscale = 1.0;
+  return (int)ceil(pil_filter_support(filter) * filterscale) * 2 + 1;
+}
+
+extern "C" int mp_pil_resample_coeffs(int filter, int in_size, int out_size, int* bounds, int* coefs, int ksize) {
+  MP_REQUIRE(filter == 2 || filter == 3, MP_ERR_ARG, "mp_pil_resample_coeffs: filter %d is not built (2 = BILINEAR, 3 = BICUBIC)", filter);
+  MP_REQUIRE(in_size > 0 && out_size > 0 && bounds && coefs, MP_ERR_ARG, "mp_pil_resample_coeffs: bad arguments");
+  MP_REQUIRE(ksize == mp_pil_resample_ksize(filter, in_size, out_size), MP_ERR_SHAPE, "mp_pil_resample_coeffs: ksize must be %d",
+             mp_pil_resample_ksize(filter, in_size, out_size));
+  // Resample.c precompute_coeffs over the box (0, in_size) + normalize_coeffs_8bpc
+  const float in0 = 0.0f, in1 = (float)in_size;
+  double scale, filterscale;
+  filterscale = scale = (double)(in1 - in0) / out_size;
+  if (filterscale < 1.0) filterscale = 1.0;
+  const double support = pil_filter_support(filter) * filterscale;
+  const double ss = 1.0 / filterscale;
+  double* k = new double[ksize];
+  for (int xx = 0; xx < out_size; ++xx) {
+    const double center = in0 + (xx + 0.5) * scale;
+    double ww = 0.0;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in_size) xmax = in_size;
+    xmax -= xmin;
+    for (int x = 0; x < xmax; ++x) {
+      const double wgt = pil_filter_weight(filter, (x + xmin - center + 0.5) * ss);
+      k[x] = wgt;
+      ww += wgt;
+    }
+    for (int x = 0; x < xmax; ++x)
+      if (ww != 0.0) k[x] /= ww;
+    for (int x = 0; x < ksize; ++x) {
+      const double v = x < xmax ? k[x] : 0.0;
+      coefs[(int64_t)xx * ksize + x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS)) : (int)(0.5 + v * (1 << PRECISION_BITS));
+    }
+    bounds[2 * xx] = xmin;
+    bounds[2 * xx + 1] = xmax;
+  }
+  delete[] k;
+  return MP_OK;
+}
+
 extern "C" int mp_resample_axis_u8(const void* src, void* dst, int64_t outer, int in_len, int out_len, int64_t inner,
                                    const int* bounds, const int* coefs, int ksize, hipStream_t stream) {
   MP_REQUIRE(outer > 0 && in_len > 0 && out_len > 0 && inner > 0 && ksize > 0, MP_ERR_SHAPE, "mp_resample_axis_u8: bad shape");
@@ -180,6 +253,23 @@ extern "C" int mp_image_table_pad_chw(const void* src, int h, int w, int C, cons
     hipLaunchKernelGGL(image_table_pad_chw_kernel<bf16_t>, grid, blk, 0, stream, (const uint8_t*)src, h, w, C, table, pad,
                        (bf16_t*)dst, size_h, size_w, top, left);
   return mp_check_launch("mp_image_table_pad_chw");
+}
+
+extern "C" int mp_image_table_crop_chw(const void* src, int h, int w, int C, const float* table, void* dst, int crop_h, int crop_w,
+                                       int top, int left, int out_dtype, hipStream_t stream) {
+  MP_REQUIRE(h > 0 && w > 0 && C > 0 && crop_h > 0 && crop_w > 0 && top >= 0 && left >= 0 && top + crop_h <= h && left + crop_w <= w,
+             MP_ERR_SHAPE, "mp_image_table_crop_chw: the %d x %d crop at (%d, %d) does not fit the %d x %d image", crop_h, crop_w, top, left,
+             h, w);
+  MP_REQUIRE(out_dtype == MP_BF16 || out_dtype == MP_F32, MP_ERR_DTYPE, "mp_image_table_crop_chw: bad out dtype");
+  const int64_t total = (int64_t)C * crop_h * crop_w;
+  const dim3 grid((unsigned)mp_cdiv(total, 256)), blk(256);
+  if (out_dtype == MP_F32)
+    hipLaunchKernelGGL(image_table_crop_chw_kernel<float>, grid, blk, 0, stream, (const uint8_t*)src, w, C, table, (float*)dst, crop_h,
+                       crop_w, top, left);
+  else
+    hipLaunchKernelGGL(image_table_crop_chw_kernel<bf16_t>, grid, blk, 0, stream, (const uint8_t*)src, w, C, table, (bf16_t*)dst,
+                       crop_h, crop_w, top, left);
+  return mp_check_launch("mp_image_table_crop_chw");
 }
 
 extern "C" int mp_overlay_mask_u8(const void* img, const void* mask, void* out, int64_t n_pixels, float tint_r, float tint_g,

@@ -3,7 +3,13 @@
 Mirrors `CLIPVisionTower.forward` + `feature_select` (model/medplib/model/multimodal_encoder/clip_encoder.py:31-60: frozen,
 hidden_states[mm_vision_select_layer], drop CLS) and HF-4.31 CLIPVisionModel arithmetic, then
 `mm_projector` mlp2x_gelu (multimodal_projector/builder.py:39-46).  Only the layers hidden_states[select_layer]
-depends on are run (the reference also runs the unused last layer)."""
+depends on are run (the reference also runs the unused last layer).
+
+`encode_pooled` is the other use of the tower: the image embedding of the retrieval of in-context examples (model/rag/image_rag.py),
+which runs every layer and pools the last hidden state; `from_vision_dir` loads a standalone `CLIPVisionModel` directory for it."""
+import json
+import os
+
 import torch
 
 from .. import ops
@@ -70,6 +76,8 @@ class ClipTower:
             put(lw["o_w"], sd[lp + "self_attn.out_proj.weight"]); put(lw["o_b"], sd[lp + "self_attn.out_proj.bias"])
             put(lw["fc1_w"], sd[lp + "mlp.fc1.weight"]); put(lw["fc1_b"], sd[lp + "mlp.fc1.bias"])
             put(lw["fc2_w"], sd[lp + "mlp.fc2.weight"]); put(lw["fc2_b"], sd[lp + "mlp.fc2.bias"])
+        if proj_prefix is None:                # a standalone CLIPVisionModel: the tower alone
+            return
         put(self.proj["w0"], sd[proj_prefix + "0.weight"]); put(self.proj["b0"], sd[proj_prefix + "0.bias"])
         put(self.proj["w2"], sd[proj_prefix + "2.weight"]); put(self.proj["b2"], sd[proj_prefix + "2.bias"])
         if "model.region_fea_adapter.weight" in sd:
@@ -132,3 +140,70 @@ class ClipTower:
     def region_feature_map(self, raw_rows):
         """region_fea_adapter over raw tower features [rows, C] -> [rows, hidden] (medplib_arch.py:207)."""
         return ops.gemm(raw_rows, self.region_adapter["w"], bias=self.region_adapter["b"])
+
+    @torch.no_grad()
+    def encode_pooled(self, images):
+        """images [n,3,H,W] (bf16 or f32) -> [n, C] f32: ALL clip_num_layers layers (HF CLIPVisionModel.last_hidden_state, no
+        post-layernorm), the bf16 mean of the patch rows (CLS dropped), L2-normalised (image_rag.py ImageRAGEncoder.encode_paths)."""
+        cfg = self.cfg
+        n = images.shape[0]
+        C, NP, H = cfg.clip_hidden_size, cfg.clip_num_patches, cfg.clip_num_heads
+        S = NP + 1
+        with ops.throughput_tiles():
+            cols = ops.patch_im2col(images.contiguous(), cfg.clip_patch_size, self.k_pad)
+            patches = ops.gemm(cols, self.patch_w)
+            x = ops.clip_embed(patches, self.cls, self.pos, n, NP, C).view(n * S, C)
+            x = ops.layernorm(x, self.pre_ln[0], self.pre_ln[1], cfg.clip_ln_eps)
+            for lw in self.layers:
+                h = ops.layernorm(x, lw["ln1"][0], lw["ln1"][1], cfg.clip_ln_eps)
+                qkv = ops.gemm(h, lw["qkv_w"], bias=lw["qkv_b"])
+                q5 = qkv.view(n, S, 3, H, C // H)
+                a = ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2])
+                x = ops.gemm(a.view(n * S, C), lw["o_w"], bias=lw["o_b"], residual=x)
+                h = ops.layernorm(x, lw["ln2"][0], lw["ln2"][1], cfg.clip_ln_eps)
+                h = ops.gemm(h, lw["fc1_w"], bias=lw["fc1_b"], act=ops.ACT_QUICK_GELU)
+                x = ops.gemm(h, lw["fc2_w"], bias=lw["fc2_b"], residual=x)
+        return ops.clip_pool_normalize(x.contiguous(), n)
+
+    @classmethod
+    def from_vision_dir(cls, path, device):
+        """A standalone HF `CLIPVisionModel` directory (config.json + weights, keys `vision_model.*`) -> a ClipTower holding its
+        weights.  Towers this build does not run are refused, naming the config field."""
+        from ..surface import _read_weight_files
+        cfg = vision_config_from_dir(path)
+        sd = _read_weight_files(path)
+        if not sd:
+            raise FileNotFoundError(f"{path}: no pytorch_model*.bin or *.safetensors weights")
+        if not any(k.startswith("vision_model.") for k in sd):       # transformers >= 5 saves a CLIPVisionModel without the prefix
+            sd = {"vision_model." + k: v for k, v in sd.items()}
+        if "vision_model.embeddings.patch_embedding.weight" not in sd:
+            raise ValueError(f"{path}: no `vision_model.embeddings.patch_embedding.weight` (not a CLIP vision tower)")
+        tower = cls(cfg, device)
+        tower.load_hf(sd, tower_prefix="vision_model.", proj_prefix=None)
+        return tower
+
+
+def vision_config_from_dir(path):
+    """config.json of a CLIP vision tower directory (CLIPVisionModel, or a CLIPModel's `vision_config`) -> MedPLIBConfig with the
+    tower's dims.  The tower runs bf16 ViTs with head_dim 64, quick_gelu, 3 input channels and hidden / intermediate sizes that are
+    multiples of 64; anything else raises ValueError naming the field."""
+    from .config import MedPLIBConfig
+    raw = json.load(open(os.path.join(path, "config.json")))
+    t = raw.get("vision_config", raw)
+    mt = t.get("model_type", raw.get("model_type"))
+    if mt not in ("clip_vision_model", "clip"):
+        raise ValueError(f"{path}: config.json model_type={mt!r}; only CLIP vision towers (clip_vision_model) are built")
+    C, heads = int(t.get("hidden_size", 768)), int(t.get("num_attention_heads", 12))
+    inter, img, patch = int(t.get("intermediate_size", 3072)), int(t.get("image_size", 224)), int(t.get("patch_size", 32))
+    checks = (("hidden_act", t.get("hidden_act", "quick_gelu") == "quick_gelu", "must be quick_gelu"),
+              ("num_channels", int(t.get("num_channels", 3)) == 3, "must be 3"),
+              ("num_attention_heads", heads > 0 and C % heads == 0 and C // heads == 64, "hidden_size / num_attention_heads must be 64"),
+              ("hidden_size", C % 64 == 0, "must be a multiple of 64"),
+              ("intermediate_size", inter % 64 == 0, "must be a multiple of 64"),
+              ("image_size", img % patch == 0, "must be a multiple of patch_size"))
+    for field, ok, why in checks:
+        if not ok:
+            raise ValueError(f"{path}: config.json {field}={t.get(field)!r} is not supported by the CLIP tower ({why})")
+    return MedPLIBConfig(hidden_size=64, intermediate_size=64, clip_image_size=img, clip_patch_size=patch, clip_hidden_size=C,
+                         clip_intermediate_size=inter, clip_num_layers=int(t.get("num_hidden_layers", 12)), clip_num_heads=heads,
+                         clip_ln_eps=float(t.get("layer_norm_eps", 1e-5)), mm_vision_select_layer=-1)

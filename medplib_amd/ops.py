@@ -1659,3 +1659,50 @@ def adamw_step(p, g, m, v, lr, beta1, beta2, eps, wd, step, max_norm=0.0, grad_s
         _chk(t, torch.float32, "adamw"); assert t.is_contiguous()
     lib().call("mp_adamw_step_f32", _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
                float(wd), int(step), float(max_norm), _p(grad_sumsq), float(grad_scale), _stream())
+
+
+# ------------------------------------------------------------------ retrieval of in-context examples (medplib_amd/rag.py) ------------
+TOPK_MAX = 64
+
+
+def dot_topk_workspace_bytes(N, Q, C, k):
+    return int(lib().raw("mp_dot_topk_workspace_bytes")(int(N), int(Q), int(C), int(k)))
+
+
+def dot_topk(index, queries, k, workspace=None):
+    """Exact fp32 inner-product top-k.  index [N, C] f32 (rows may be strided), queries [Q, C] f32 -> (scores [Q, k] f32, idx [Q, k]
+    int32), descending score, ties to the lower index, (-inf, -1) past N.  Limits: 1 <= k <= 64, C % 4 == 0, N < 2^31."""
+    _chk(index, torch.float32, "dot_topk.index"); _chk(queries, torch.float32, "dot_topk.queries")
+    assert index.dim() == 2 and queries.dim() == 2 and index.shape[1] == queries.shape[1], "dot_topk: index [N, C], queries [Q, C]"
+    assert index.stride(1) == 1, "dot_topk: index rows must be contiguous"
+    queries = queries.contiguous()
+    N, C = index.shape
+    Q = queries.shape[0]
+    scores = torch.empty((Q, k), dtype=torch.float32, device=queries.device)
+    idx = torch.empty((Q, k), dtype=torch.int32, device=queries.device)
+    need = dot_topk_workspace_bytes(N, Q, C, k)
+    if need < 0:                          # a shape beyond the limits: let the library name it
+        need = 8
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=queries.device)
+    lib().call("mp_dot_topk_f32", _p(index), index.stride(0), _p(queries), N, Q, C, int(k), _p(scores), _p(idx), _p(workspace),
+               workspace.numel(), _stream())
+    return scores, idx
+
+
+def clip_pool_normalize(hidden, n):
+    """Last hidden state [n * S, C] bf16 (CLS first in every image) -> [n, C] f32: bf16 mean of the patch rows, L2-normalised."""
+    _chk(hidden, torch.bfloat16, "clip_pool_normalize"); assert hidden.is_contiguous() and hidden.dim() == 2
+    rows, C = hidden.shape
+    assert rows % n == 0, "clip_pool_normalize: rows must be n * S"
+    out = torch.empty((n, C), dtype=torch.float32, device=hidden.device)
+    lib().call("mp_clip_pool_normalize_bf16", _p(hidden), n, rows // n, C, _p(out), _stream())
+    return out
+
+
+def l2_normalize_rows(x, out=None):
+    """x [rows, C] f32 -> x / (||x||_2 + 1e-12) per row (out may be x)."""
+    _chk(x, torch.float32, "l2_normalize_rows"); assert x.is_contiguous() and x.dim() == 2
+    out = torch.empty_like(x) if out is None else out
+    lib().call("mp_l2_normalize_rows_f32", _p(x), _p(out), x.shape[0], x.shape[1], _stream())
+    return out

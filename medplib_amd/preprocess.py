@@ -146,3 +146,82 @@ def overlay_mask(img_rgb, mask):
     out = torch.empty_like(img_rgb)
     lib().call("mp_overlay_mask_u8", ops._p(img_rgb), ops._p(mask), ops._p(out), mask.numel(), *ICL_TINT, ops._stream())
     return out
+
+
+# ------------------------------------------------------------------ CLIPImageProcessor (retrieval of in-context examples) --------
+PIL_BILINEAR, PIL_BICUBIC = 2, 3
+
+
+def resample_coeffs_host(filt, in_size, out_size):
+    """Pillow's bounds and fixed-point coefficients of one axis for filter id `filt` (2 bilinear, 3 bicubic) -> (bounds, coefs) int32."""
+    L = lib()
+    k = L._raw_mp_pil_resample_ksize(int(filt), in_size, out_size)
+    bounds = np.empty((out_size, 2), dtype=np.int32)
+    coefs = np.empty((out_size, max(k, 1)), dtype=np.int32)
+    L.call("mp_pil_resample_coeffs", int(filt), in_size, out_size, bounds.ctypes.data_as(ctypes.c_void_p),
+           coefs.ctypes.data_as(ctypes.c_void_p), k)
+    return bounds, coefs
+
+
+@functools.lru_cache(maxsize=256)
+def _axis_tables_filter(filt, in_size, out_size, device):
+    b, c = resample_coeffs_host(filt, in_size, out_size)
+    return (torch.from_numpy(b).to(device), torch.from_numpy(c).to(device), c.shape[1])
+
+
+def resize_u8(img, out_h, out_w, filt):
+    """PIL Image.resize((out_w, out_h), filt) of a CUDA uint8 [H, W, C] tensor, bit-exact (an axis that keeps its size is not touched,
+    as in Pillow)."""
+    assert img.is_cuda and img.dtype == torch.uint8 and img.dim() == 3, "resize_u8: CUDA uint8 HWC tensor"
+    x = img.contiguous()
+    H, W, C = x.shape
+    dev = str(x.device)
+    if W != out_w:
+        b, c, k = _axis_tables_filter(filt, W, out_w, dev)
+        y = torch.empty((H, out_w, C), dtype=torch.uint8, device=x.device)
+        lib().call("mp_resample_axis_u8", ops._p(x), ops._p(y), H, W, out_w, C, ops._p(b), ops._p(c), k, ops._stream())
+        x = y
+    if H != out_h:
+        b, c, k = _axis_tables_filter(filt, H, out_h, dev)
+        y = torch.empty((out_h, out_w, C), dtype=torch.uint8, device=x.device)
+        lib().call("mp_resample_axis_u8", ops._p(x), ops._p(y), 1, H, out_h, out_w * C, ops._p(b), ops._p(c), k, ops._stream())
+        x = y
+    return x
+
+
+def clip_processor_resize_shape(h, w, shortest_edge):
+    """CLIPImageProcessor's output size for {"shortest_edge": s}: the short side becomes s, the long side int(s * long / short)."""
+    short, long = (w, h) if w <= h else (h, w)
+    new_long = int(shortest_edge * long / short)
+    return (new_long, shortest_edge) if w <= h else (shortest_edge, new_long)
+
+
+@functools.lru_cache(maxsize=8)
+def _processor_table(mean, std, rescale_factor, device):
+    """[3, 256] f32: uint8 -> (float32(x * rescale_factor in float64) - mean) / std in float32 (CLIPImageProcessor rescale + normalize)."""
+    x = np.arange(256, dtype=np.uint8)
+    r = (x.astype(np.float64) * rescale_factor).astype(np.float32)
+    tab = (r[None, :] - np.array(mean, dtype=np.float32)[:, None]) / np.array(std, dtype=np.float32)[:, None]
+    return torch.from_numpy(tab.astype(np.float32)).contiguous().to(device)
+
+
+def preprocess_clip_processor(img_rgb, shortest_edge=336, crop=336, mean=CLIP_MEAN, std=CLIP_STD, out_dtype=torch.float32,
+                              resample=PIL_BICUBIC, rescale_factor=1 / 255):
+    """CUDA uint8 [H, W, 3] RGB -> [3, crop_h, crop_w]: CLIPImageProcessor (do_resize shortest edge with PIL BICUBIC, centre crop,
+    rescale, normalise) bit for bit in float32.  Only resample = 3 (bicubic), the processor's setting for every CLIP checkpoint, is
+    built."""
+    if int(resample) != PIL_BICUBIC:
+        raise NotImplementedError(f"preprocess_clip_processor: resample={resample} is not built; only 3 (PIL BICUBIC)")
+    assert img_rgb.is_cuda and img_rgb.dtype == torch.uint8 and img_rgb.dim() == 3 and img_rgb.shape[2] == 3, \
+        "preprocess_clip_processor: CUDA uint8 [H, W, 3] tensor"
+    ch, cw = (crop, crop) if isinstance(crop, int) else (int(crop[0]), int(crop[1]))
+    h, w = int(img_rgb.shape[0]), int(img_rgb.shape[1])
+    nh, nw = clip_processor_resize_shape(h, w, int(shortest_edge))
+    r = resize_u8(img_rgb, nh, nw, PIL_BICUBIC)
+    if nh < ch or nw < cw:
+        raise NotImplementedError(f"preprocess_clip_processor: a crop of {ch} x {cw} from {nh} x {nw} would pad; not built")
+    tab = _processor_table(tuple(float(v) for v in mean), tuple(float(v) for v in std), float(rescale_factor), str(img_rgb.device))
+    out = torch.empty((3, ch, cw), dtype=out_dtype, device=img_rgb.device)
+    lib().call("mp_image_table_crop_chw", ops._p(r), nh, nw, 3, ops._p(tab), ops._p(out), ch, cw, (nh - ch) // 2, (nw - cw) // 2,
+               ops._dt(out_dtype), ops._stream())
+    return out
