@@ -63,6 +63,11 @@ int mp_gemm_bf16_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void
  * plain weight followed by mp_rope_qk_bf16.  head_dim 128, hidden % 256 == 0. */
 int mp_gemm_qkv_rope_bf16(const void* A, int64_t lda, const void* Wi, int64_t ldw, void* C, int64_t ldc, const float* cos_t,
                           const float* sin_t, int M, int N, int K, int seq, int pos_offset, int head_dim, hipStream_t stream);
+/* mp_gemm_qkv_rope_bf16 with the row count of cos_t / sin_t: returns MP_ERR_SHAPE (mp_last_error_string says why) before any launch when
+ * seq + pos_offset > table_rows or pos_offset < 0, MP_ERR_ARG for a null table.  Same bits as mp_gemm_qkv_rope_bf16 otherwise. */
+int mp_gemm_qkv_rope_bounded_bf16(const void* A, int64_t lda, const void* Wi, int64_t ldw, void* C, int64_t ldc, const float* cos_t,
+                                  const float* sin_t, int M, int N, int K, int seq, int pos_offset, int head_dim, int table_rows,
+                                  hipStream_t stream);
 /* The gate|up projection of a training forward (HF LlamaMLP, medplib_moe_llama.py:127-141, with peft adapters folded into K: see
  * mp_lora_down_bf16): act_out[M, N/2] = silu(gate) * up as with MP_ACT_SWIGLU_PAIR, and gu_out[M, N] = the bf16 gate|up values in W's
  * interleaved row order (what mp_swiglu_pair_bwd_bf16 reads).  Same values as mp_gemm_bf16_nt + mp_swiglu_pair_fwd_bf16. */
@@ -131,6 +136,17 @@ int mp_gemv_rmsnorm_rope_append_bf16(const void* x, int64_t ldx, const float* no
                                      int64_t ldy, const float* cos_t, const float* sin_t, void* cache_k, void* cache_v, const int* pos_dev,
                                      int M, int heads, int head_dim, int K, int64_t cache_batch_stride, int64_t cache_seq_stride,
                                      hipStream_t stream);
+/* Bit flags of the sticky int32 error word the bounded decode entry points OR into (never cleared by the library). */
+#define MP_POS_ERR_TABLE 1   /* *pos_dev outside [0, table_rows): no RoPE row */
+#define MP_POS_ERR_CACHE 2   /* *pos_dev outside [0, cache_rows): no KV-cache row */
+/* mp_gemv_rmsnorm_rope_append_bf16 bounded on the device: table_rows = rows of cos_t / sin_t, cache_rows = max_len of the caches, err = an
+ * int32 error word in device memory.  When *pos_dev is outside [0, table_rows) or [0, cache_rows) the launch reads no table row and writes
+ * nothing (neither q nor the caches) and ORs MP_POS_ERR_TABLE / MP_POS_ERR_CACHE into *err; it does not trap.  In range: the bits of the
+ * unbounded entry point.  table_rows, cache_rows > 0 and a non-null err, else MP_ERR_SHAPE / MP_ERR_ARG before any launch. */
+int mp_gemv_rmsnorm_rope_append_bounded_bf16(const void* x, int64_t ldx, const float* norm_w, float eps, const void* W_qkv, int64_t ldw,
+                                             void* qkv, int64_t ldy, const float* cos_t, const float* sin_t, void* cache_k, void* cache_v,
+                                             const int* pos_dev, int M, int heads, int head_dim, int K, int64_t cache_batch_stride,
+                                             int64_t cache_seq_stride, int table_rows, int cache_rows, int* err, hipStream_t stream);
 
 /* Optional scratch for the 256x256 kernel's tail split-K (the last partial wave of tiles is cut along K so it does not hold
  * the machine for a whole tile-time): `ws` >= 64 MiB of device memory, `tickets` >= 384 ZEROED device ints.  The library never
@@ -159,12 +175,22 @@ int mp_layernorm_bf16(const void* x, int64_t ldx, const float* w, const float* b
 /* Half-split RoPE on the q and k thirds of a fused [tokens, 3*H*D] buffer. */
 int mp_rope_qk_bf16(void* qkv, int64_t ld, const float* cos_t, const float* sin_t, int64_t tokens, int seq, int heads,
                     int head_dim, int pos_offset, hipStream_t stream);
+/* mp_rope_qk_bf16 with the row count of cos_t / sin_t: MP_ERR_SHAPE before any launch when seq + pos_offset > table_rows or
+ * pos_offset < 0, MP_ERR_ARG for a null operand.  Same bits as mp_rope_qk_bf16 otherwise. */
+int mp_rope_qk_bounded_bf16(void* qkv, int64_t ld, const float* cos_t, const float* sin_t, int64_t tokens, int seq, int heads,
+                            int head_dim, int pos_offset, int table_rows, hipStream_t stream);
 /* One decode step of the KV-cache path (prepare_inputs_for_generation + LlamaAttention with past_key_value, medplib_moe_llama.py:
  * 451-485; HF 4.31): RoPE of the single new token of each sequence at position *pos_dev (device), q rotated in place inside the
  * fused qkv row, rotated k and v appended to the caches at that position.  mp_advance_ints bumps the device-side counters. */
 int mp_decode_rope_append_bf16(void* qkv, int64_t ld, const float* cos_t, const float* sin_t, void* cache_k, void* cache_v,
                                const int* pos_dev, int B, int heads, int head_dim, int64_t cache_batch_stride, int64_t cache_seq_stride,
                                hipStream_t stream);
+/* mp_decode_rope_append_bf16 bounded on the device (as mp_gemv_rmsnorm_rope_append_bounded_bf16): a position outside [0, table_rows) or
+ * [0, cache_rows) reads no table row, writes nothing and ORs MP_POS_ERR_* into *err (int32, device memory); no trap.  In range: the bits of
+ * the unbounded entry point.  table_rows, cache_rows > 0 and non-null operands, else MP_ERR_SHAPE / MP_ERR_ARG before any launch. */
+int mp_decode_rope_append_bounded_bf16(void* qkv, int64_t ld, const float* cos_t, const float* sin_t, void* cache_k, void* cache_v,
+                                       const int* pos_dev, int B, int heads, int head_dim, int64_t cache_batch_stride,
+                                       int64_t cache_seq_stride, int table_rows, int cache_rows, int* err, hipStream_t stream);
 int mp_advance_ints(int* p, int n, int delta, hipStream_t stream);
 /* greedy next-token pick over fp32 logits (HF generate do_sample=False, MedPLIB.py:592-606). */
 int mp_argmax_rows_f32(const float* x, int64_t ld, int64_t rows, int cols, int64_t* out, hipStream_t stream);
@@ -409,6 +435,10 @@ int mp_rmsnorm_gate_rstd_bf16(const void* x, int64_t ldx, const float* ln_w, flo
 int mp_gemm_qkv_rope_scaled_bf16(const void* A, int64_t lda, const void* Wi, int64_t ldw, void* C, int64_t ldc, const float* cos_t,
                                  const float* sin_t, const float* row_scale, int M, int N, int K, int seq, int pos_offset, int head_dim,
                                  hipStream_t stream);
+/* mp_gemm_qkv_rope_scaled_bf16 with the row count of cos_t / sin_t (as mp_gemm_qkv_rope_bounded_bf16). */
+int mp_gemm_qkv_rope_scaled_bounded_bf16(const void* A, int64_t lda, const void* Wi, int64_t ldw, void* C, int64_t ldc, const float* cos_t,
+                                         const float* sin_t, const float* row_scale, int M, int N, int K, int seq, int pos_offset,
+                                         int head_dim, int table_rows, hipStream_t stream);
 int mp_gemm_bf16_nt_batched_rows_scaled(const void* A, int64_t lda, const int* a_rows, const float* a_row_scale, const void* W, int64_t ldw,
                                         int64_t strideW, void* C, int64_t ldc, int64_t strideC, int rows_stride, int batch, int M, int N,
                                         int K, const int* m_dev, hipStream_t stream);

@@ -14,6 +14,11 @@
 #define MP_BF16 0
 #define MP_F32 1
 
+// bits the bounded decode RoPE / KV-append kernels OR into their sticky device error word (include/medplib_hip.h)
+#define MP_POS_ERR_TABLE 1         // position outside [0, table_rows): no RoPE row to read
+#define MP_POS_ERR_CACHE 2         // position outside [0, cache_rows): no KV-cache row to write
+#define MP_POS_UNBOUNDED 0x7fffffff   // table_rows / cache_rows of the unbounded entry points
+
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;

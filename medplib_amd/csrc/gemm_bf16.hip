@@ -539,6 +539,32 @@ extern "C" int mp_gemm_qkv_rope_scaled_bf16(const void* A, int64_t lda, const vo
   return mp_launch_gemm320(g, 1, stream);
 }
 
+// mp_gemm_qkv_rope_bf16 / _scaled_ with the RoPE table's row count known on the host: every position (row % seq) + pos_offset must
+// have a row, otherwise MP_ERR_SHAPE before any launch
+static int qkv_rope_bound_check(const char* name, const float* cos_t, const float* sin_t, int seq, int pos_offset, int table_rows) {
+  MP_REQUIRE(cos_t && sin_t, MP_ERR_ARG, "%s: null RoPE table", name);
+  MP_REQUIRE(pos_offset >= 0 && seq > 0 && (int64_t)seq + pos_offset <= table_rows, MP_ERR_SHAPE,
+             "%s: positions up to seq + pos_offset = %lld need that many RoPE table rows (table_rows = %d)", name,
+             (long long)seq + pos_offset, table_rows);
+  return MP_OK;
+}
+
+extern "C" int mp_gemm_qkv_rope_bounded_bf16(const void* A, int64_t lda, const void* Wi, int64_t ldw, void* C, int64_t ldc,
+                                             const float* cos_t, const float* sin_t, int M, int N, int K, int seq, int pos_offset,
+                                             int head_dim, int table_rows, hipStream_t stream) {
+  const int rc = qkv_rope_bound_check("mp_gemm_qkv_rope_bounded_bf16", cos_t, sin_t, seq, pos_offset, table_rows);
+  if (rc != MP_OK) return rc;
+  return mp_gemm_qkv_rope_bf16(A, lda, Wi, ldw, C, ldc, cos_t, sin_t, M, N, K, seq, pos_offset, head_dim, stream);
+}
+
+extern "C" int mp_gemm_qkv_rope_scaled_bounded_bf16(const void* A, int64_t lda, const void* Wi, int64_t ldw, void* C, int64_t ldc,
+                                                    const float* cos_t, const float* sin_t, const float* row_scale, int M, int N, int K,
+                                                    int seq, int pos_offset, int head_dim, int table_rows, hipStream_t stream) {
+  const int rc = qkv_rope_bound_check("mp_gemm_qkv_rope_scaled_bounded_bf16", cos_t, sin_t, seq, pos_offset, table_rows);
+  if (rc != MP_OK) return rc;
+  return mp_gemm_qkv_rope_scaled_bf16(A, lda, Wi, ldw, C, ldc, cos_t, sin_t, row_scale, M, N, K, seq, pos_offset, head_dim, stream);
+}
+
 // gate|up projection of a TRAINING forward: act = silu(gate) * up from the fused epilogue AND the bf16 gate|up values themselves (the
 // backward's operands), one launch instead of GEMM + mp_swiglu_pair_fwd_bf16 (which re-read the [tokens, 2 ff] tensor).
 extern "C" int mp_gemm_swiglu_keep_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* act_out, int64_t ld_act, void* gu_out,

@@ -465,6 +465,8 @@ struct RopeArgs {
   const int* pos_dev;
   int H, D;
   int64_t c_sb, c_ss;
+  int table_rows, cache_rows;                // bounded entry point: a position outside either bound reads / writes nothing and
+  int* err;                                  // wave 0 ORs MP_POS_ERR_* into *err (the unbounded one: MP_POS_UNBOUNDED, nullptr)
 };
 
 template <int M, int NCH>
@@ -490,6 +492,11 @@ __global__ __launch_bounds__(256) void gemv_rmsnorm_rope_kernel(GemvArgs g, cons
   gv_norm_rows_dot_any<M, NCH, true>(g, nw, eps, wp, lane, wv, acc);      // overlapped trips: one round of workgroups in lockstep (see the core)
   if (lane != 0 || idle) return;
   const int pos = ra.pos_dev[0];
+  if (pos < 0 || pos >= ra.table_rows || pos >= ra.cache_rows) {
+    if (wid == 0 && ra.err)
+      atomicOr(ra.err, (pos < 0 || pos >= ra.table_rows ? MP_POS_ERR_TABLE : 0) | (pos < 0 || pos >= ra.cache_rows ? MP_POS_ERR_CACHE : 0));
+    return;
+  }
 #pragma unroll
   for (int m = 0; m < M; ++m) {
     float v[4];
@@ -764,17 +771,18 @@ extern "C" int mp_gemv_rmsnorm_bf16(const void* x, int64_t ldx, const float* nor
   return mp_check_launch("mp_gemv_rmsnorm_bf16");
 }
 
-extern "C" int mp_gemv_rmsnorm_rope_append_bf16(const void* x, int64_t ldx, const float* norm_w, float eps, const void* W_qkv, int64_t ldw,
-                                                void* qkv, int64_t ldy, const float* cos_t, const float* sin_t, void* cache_k, void* cache_v,
-                                                const int* pos_dev, int M, int heads, int head_dim, int K, int64_t cache_batch_stride,
-                                                int64_t cache_seq_stride, hipStream_t stream) {
+static int gemv_rmsnorm_rope_launch(const char* name, const void* x, int64_t ldx, const float* norm_w, float eps, const void* W_qkv,
+                                    int64_t ldw, void* qkv, int64_t ldy, const float* cos_t, const float* sin_t, void* cache_k, void* cache_v,
+                                    const int* pos_dev, int M, int heads, int head_dim, int K, int64_t cache_batch_stride,
+                                    int64_t cache_seq_stride, int table_rows, int cache_rows, int* err, hipStream_t stream) {
   MP_REQUIRE(M >= 1 && M <= 2 && heads > 0 && head_dim % 16 == 0 && K >= 512 && K % 512 == 0 && K <= 8192 && ldx % 8 == 0 && ldw % 8 == 0,
-             MP_ERR_SHAPE, "mp_gemv_rmsnorm_rope_append_bf16: 1 <= M <= 2, head_dim %% 16 == 0, K a multiple of 512 up to 8192");
-  MP_REQUIRE(norm_w && cos_t && sin_t && cache_k && cache_v && pos_dev, MP_ERR_ARG, "mp_gemv_rmsnorm_rope_append_bf16: null operand");
+             MP_ERR_SHAPE, "%s: 1 <= M <= 2, head_dim %% 16 == 0, K a multiple of 512 up to 8192", name);
+  MP_REQUIRE(norm_w && cos_t && sin_t && cache_k && cache_v && pos_dev, MP_ERR_ARG, "%s: null operand", name);
   const int N = 3 * heads * head_dim;
   GemvArgs g{(const bf16_t*)x, ldx, (const bf16_t*)W_qkv, ldw, 0, qkv, ldy, nullptr, nullptr, 0, nullptr, nullptr, nullptr, M, N, K, ACT_NONE,
              0, 1.f};
-  RopeArgs ra{cos_t, sin_t, (bf16_t*)cache_k, (bf16_t*)cache_v, pos_dev, heads, head_dim, cache_batch_stride, cache_seq_stride};
+  RopeArgs ra{cos_t, sin_t, (bf16_t*)cache_k, (bf16_t*)cache_v, pos_dev, heads, head_dim, cache_batch_stride, cache_seq_stride,
+              table_rows, cache_rows, err};
   const dim3 grid((unsigned)mp_cdiv(N / 4, 4));
 #define MP_GVR(MM, NC) hipLaunchKernelGGL((gemv_rmsnorm_rope_kernel<MM, NC>), grid, dim3(256), 0, stream, g, norm_w, eps, ra)
 #define MP_GVR_M(NC) do { if (M == 1) MP_GVR(1, NC); else MP_GVR(2, NC); } while (0)
@@ -784,9 +792,31 @@ extern "C" int mp_gemv_rmsnorm_rope_append_bf16(const void* x, int64_t ldx, cons
     case 4: MP_GVR_M(4); break;
     case 8: MP_GVR_M(8); break;
     case 16: MP_GVR_M(16); break;
-    default: MP_REQUIRE(false, MP_ERR_SHAPE, "mp_gemv_rmsnorm_rope_append_bf16: K / 512 must be 1, 2, 4, 8 or 16 (K=%d)", K);
+    default: MP_REQUIRE(false, MP_ERR_SHAPE, "%s: K / 512 must be 1, 2, 4, 8 or 16 (K=%d)", name, K);
   }
 #undef MP_GVR_M
 #undef MP_GVR
-  return mp_check_launch("mp_gemv_rmsnorm_rope_append_bf16");
+  return mp_check_launch(name);
+}
+
+extern "C" int mp_gemv_rmsnorm_rope_append_bf16(const void* x, int64_t ldx, const float* norm_w, float eps, const void* W_qkv, int64_t ldw,
+                                                void* qkv, int64_t ldy, const float* cos_t, const float* sin_t, void* cache_k, void* cache_v,
+                                                const int* pos_dev, int M, int heads, int head_dim, int K, int64_t cache_batch_stride,
+                                                int64_t cache_seq_stride, hipStream_t stream) {
+  return gemv_rmsnorm_rope_launch("mp_gemv_rmsnorm_rope_append_bf16", x, ldx, norm_w, eps, W_qkv, ldw, qkv, ldy, cos_t, sin_t, cache_k,
+                                  cache_v, pos_dev, M, heads, head_dim, K, cache_batch_stride, cache_seq_stride, MP_POS_UNBOUNDED,
+                                  MP_POS_UNBOUNDED, nullptr, stream);
+}
+
+extern "C" int mp_gemv_rmsnorm_rope_append_bounded_bf16(const void* x, int64_t ldx, const float* norm_w, float eps, const void* W_qkv,
+                                                        int64_t ldw, void* qkv, int64_t ldy, const float* cos_t, const float* sin_t,
+                                                        void* cache_k, void* cache_v, const int* pos_dev, int M, int heads, int head_dim,
+                                                        int K, int64_t cache_batch_stride, int64_t cache_seq_stride, int table_rows,
+                                                        int cache_rows, int* err, hipStream_t stream) {
+  MP_REQUIRE(table_rows > 0 && cache_rows > 0, MP_ERR_SHAPE,
+             "mp_gemv_rmsnorm_rope_append_bounded_bf16: table_rows (%d) and cache_rows (%d) must be > 0", table_rows, cache_rows);
+  MP_REQUIRE(x && W_qkv && qkv && err, MP_ERR_ARG, "mp_gemv_rmsnorm_rope_append_bounded_bf16: null operand");
+  return gemv_rmsnorm_rope_launch("mp_gemv_rmsnorm_rope_append_bounded_bf16", x, ldx, norm_w, eps, W_qkv, ldw, qkv, ldy, cos_t, sin_t,
+                                  cache_k, cache_v, pos_dev, M, heads, head_dim, K, cache_batch_stride, cache_seq_stride, table_rows,
+                                  cache_rows, err, stream);
 }

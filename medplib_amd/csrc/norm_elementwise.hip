@@ -171,14 +171,21 @@ __global__ void rope_qk_bf16_kernel(bf16_t* __restrict__ qkv, const float* __res
 // Decode step (one new token per sequence): RoPE at the cached length read from DEVICE memory (so the launch arguments do not
 // change from token to token and the step can live in a HIP graph), q rotated in place, the rotated k and the v appended to the
 // KV cache at that position.  One thread per (sequence, head, 8 rotary pairs).
+// Bounded form (err != nullptr): a position outside [0, table_rows) or [0, cache_rows) reads no table row, writes nothing (q included)
+// and thread 0 ORs MP_POS_ERR_* into *err; the unbounded entry point passes MP_POS_UNBOUNDED and no word (its bits are unchanged).
 __global__ void decode_rope_append_kernel(bf16_t* __restrict__ qkv, int64_t ld, const float* __restrict__ cos_t,
                                           const float* __restrict__ sin_t, bf16_t* __restrict__ ck, bf16_t* __restrict__ cv,
-                                          const int* __restrict__ pos_dev, int B, int H, int D, int64_t c_sb, int64_t c_ss) {
+                                          const int* __restrict__ pos_dev, int B, int H, int D, int64_t c_sb, int64_t c_ss,
+                                          int table_rows, int cache_rows, int* __restrict__ err) {
   const int half = D / 2, per_head = half / 8;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * H * per_head) return;
   const int c = (idx % per_head) * 8, h = (idx / per_head) % H, b = idx / (per_head * H);
   const int pos = pos_dev[0];
+  if (pos < 0 || pos >= table_rows || pos >= cache_rows) {
+    if (idx == 0 && err) atomicOr(err, (pos < 0 || pos >= table_rows ? MP_POS_ERR_TABLE : 0) | (pos < 0 || pos >= cache_rows ? MP_POS_ERR_CACHE : 0));
+    return;
+  }
   const float* cs = cos_t + (int64_t)pos * half + c;
   const float* sn = sin_t + (int64_t)pos * half + c;
   bf16_t* q = qkv + (int64_t)b * ld + (int64_t)h * D;
@@ -389,15 +396,45 @@ extern "C" int mp_rope_qk_bf16(void* qkv, int64_t ld, const float* cos_t, const 
   return mp_check_launch("mp_rope_qk_bf16");
 }
 
+// prefill RoPE with the table's row count known on the host: every position (row % seq) + pos_offset must have a row
+extern "C" int mp_rope_qk_bounded_bf16(void* qkv, int64_t ld, const float* cos_t, const float* sin_t, int64_t tokens, int seq,
+                                       int heads, int head_dim, int pos_offset, int table_rows, hipStream_t stream) {
+  MP_REQUIRE(qkv && cos_t && sin_t, MP_ERR_ARG, "mp_rope_qk_bounded_bf16: null operand");
+  MP_REQUIRE(pos_offset >= 0 && seq > 0 && (int64_t)seq + pos_offset <= table_rows, MP_ERR_SHAPE,
+             "mp_rope_qk_bounded_bf16: positions up to seq + pos_offset = %lld need that many RoPE table rows (table_rows = %d)",
+             (long long)seq + pos_offset, table_rows);
+  return mp_rope_qk_bf16(qkv, ld, cos_t, sin_t, tokens, seq, heads, head_dim, pos_offset, stream);
+}
+
+static int decode_rope_append_launch(const char* name, void* qkv, int64_t ld, const float* cos_t, const float* sin_t, void* cache_k,
+                                     void* cache_v, const int* pos_dev, int B, int heads, int head_dim, int64_t cache_batch_stride,
+                                     int64_t cache_seq_stride, int table_rows, int cache_rows, int* err, hipStream_t stream) {
+  const int n = B * heads * (head_dim / 16);
+  if (n == 0) return MP_OK;
+  hipLaunchKernelGGL(decode_rope_append_kernel, dim3((unsigned)mp_cdiv(n, 256)), dim3(256), 0, stream, (bf16_t*)qkv, ld, cos_t, sin_t,
+                     (bf16_t*)cache_k, (bf16_t*)cache_v, pos_dev, B, heads, head_dim, cache_batch_stride, cache_seq_stride, table_rows,
+                     cache_rows, err);
+  return mp_check_launch(name);
+}
+
 extern "C" int mp_decode_rope_append_bf16(void* qkv, int64_t ld, const float* cos_t, const float* sin_t, void* cache_k, void* cache_v,
                                           const int* pos_dev, int B, int heads, int head_dim, int64_t cache_batch_stride,
                                           int64_t cache_seq_stride, hipStream_t stream) {
   MP_REQUIRE(head_dim % 16 == 0 && ld % 8 == 0 && pos_dev != nullptr, MP_ERR_SHAPE, "mp_decode_rope_append_bf16: bad shape");
-  const int n = B * heads * (head_dim / 16);
-  if (n == 0) return MP_OK;
-  hipLaunchKernelGGL(decode_rope_append_kernel, dim3((unsigned)mp_cdiv(n, 256)), dim3(256), 0, stream, (bf16_t*)qkv, ld, cos_t, sin_t,
-                     (bf16_t*)cache_k, (bf16_t*)cache_v, pos_dev, B, heads, head_dim, cache_batch_stride, cache_seq_stride);
-  return mp_check_launch("mp_decode_rope_append_bf16");
+  return decode_rope_append_launch("mp_decode_rope_append_bf16", qkv, ld, cos_t, sin_t, cache_k, cache_v, pos_dev, B, heads, head_dim,
+                                   cache_batch_stride, cache_seq_stride, MP_POS_UNBOUNDED, MP_POS_UNBOUNDED, nullptr, stream);
+}
+
+extern "C" int mp_decode_rope_append_bounded_bf16(void* qkv, int64_t ld, const float* cos_t, const float* sin_t, void* cache_k,
+                                                  void* cache_v, const int* pos_dev, int B, int heads, int head_dim,
+                                                  int64_t cache_batch_stride, int64_t cache_seq_stride, int table_rows, int cache_rows,
+                                                  int* err, hipStream_t stream) {
+  MP_REQUIRE(head_dim % 16 == 0 && ld % 8 == 0 && B >= 0 && heads >= 0, MP_ERR_SHAPE, "mp_decode_rope_append_bounded_bf16: bad shape");
+  MP_REQUIRE(table_rows > 0 && cache_rows > 0, MP_ERR_SHAPE, "mp_decode_rope_append_bounded_bf16: table_rows (%d) and cache_rows (%d) must be > 0",
+             table_rows, cache_rows);
+  MP_REQUIRE(qkv && cos_t && sin_t && cache_k && cache_v && pos_dev && err, MP_ERR_ARG, "mp_decode_rope_append_bounded_bf16: null operand");
+  return decode_rope_append_launch("mp_decode_rope_append_bounded_bf16", qkv, ld, cos_t, sin_t, cache_k, cache_v, pos_dev, B, heads,
+                                   head_dim, cache_batch_stride, cache_seq_stride, table_rows, cache_rows, err, stream);
 }
 
 extern "C" int mp_advance_ints(int* p, int n, int delta, hipStream_t stream) {

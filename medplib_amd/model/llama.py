@@ -13,10 +13,19 @@ import torch
 from .. import ops
 
 
-def _rope_tables(seq, head_dim, theta, device):
+def _rope_tables(seq, head_dim, theta, device, start=0):
+    """cos / sin [seq - start, head_dim / 2] fp32 of positions start .. seq - 1 (HF 4.31 LlamaRotaryEmbedding's fp32 formula)."""
     inv = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.float32) / head_dim))
-    freqs = torch.outer(torch.arange(seq, dtype=torch.float32), inv)
+    freqs = torch.outer(torch.arange(start, seq, dtype=torch.float32), inv)
     return freqs.cos().contiguous().to(device), freqs.sin().contiguous().to(device)
+
+
+ROPE_GROW_ROWS = 1024     # RoPE tables grow in whole multiples of this many rows (slowly lengthening prompts do not reallocate each call)
+
+
+def rope_rows_for(n, rows):
+    """Rows a RoPE table of `rows` rows must have to cover positions 0 .. n - 1: unchanged when it does, else n rounded up to ROPE_GROW_ROWS."""
+    return rows if n <= rows else -(-n // ROPE_GROW_ROWS) * ROPE_GROW_ROWS
 
 
 class LlamaStack:
@@ -51,6 +60,7 @@ class LlamaStack:
                 lw["down"] = rn(d, ff)
             self.layers.append(lw)
         self.cos, self.sin = _rope_tables(cfg.max_position_embeddings, cfg.head_dim, cfg.rope_theta, device)
+        self.sin_neg = None                # -sin, for the LoRA backward's transposed RoPE (llama_lora.attach); grown with the tables
         self.training = True
         self.rts_uniform_provider = None   # callable(layer_idx, T, E) -> fp32 [T,E] gate draws (RTS uniforms / top-2 Gumbel) or None
         self.gate_pass = 0                 # forward passes so far: part of the key of the stateless gate-draw generator
@@ -292,12 +302,32 @@ class LlamaStack:
             ops.gemm_batched(act, lw["down"][e].unsqueeze(0).expand(ep.ep, -1, -1), y[:, e], m_dev=counts_t[e])
         return ep.combine(y)
 
-    def new_kv_cache(self, batch, max_len):
-        """KV cache for `evaluate()`'s greedy decode (HF `use_cache=True`, MedPLIB.py:592-606): post-RoPE K and V per layer."""
+    def ensure_positions(self, n):
+        """Grow cos / sin (and sin_neg) to cover positions 0 .. n - 1, as HF 4.31's LlamaRotaryEmbedding regrows its cache past
+        max_position_embeddings.  Only the new rows are computed (same fp32 formula), the existing ones are kept as they are, so
+        every row already in use stays bit-identical.  Growth replaces the tensors: a captured graph holding the old pointers
+        would read freed memory, so callers grow before capturing (new_kv_cache)."""
+        rows = rope_rows_for(int(n), self.cos.shape[0])
+        if rows == self.cos.shape[0]:
+            return
         cfg = self.cfg
+        cos_new, sin_new = _rope_tables(rows, cfg.head_dim, cfg.rope_theta, self.device, start=self.cos.shape[0])
+        self.cos = torch.cat([self.cos, cos_new]).contiguous()
+        self.sin = torch.cat([self.sin, sin_new]).contiguous()
+        if self.sin_neg is not None:
+            self.sin_neg = (-self.sin).contiguous()
+
+    def new_kv_cache(self, batch, max_len):
+        """KV cache for `evaluate()`'s greedy decode (HF `use_cache=True`, MedPLIB.py:592-606): post-RoPE K and V per layer, and "err", the
+        int32 word the bounded decode kernels set (MP_POS_ERR_*) when a step's position has no table or cache row.  The RoPE tables are
+        grown to max_len HERE, before _decode_graph captures their pointers (growing after the capture would leave the graph reading the
+        freed tables)."""
+        cfg = self.cfg
+        self.ensure_positions(max_len)
         shape = (batch, max_len, cfg.num_attention_heads, cfg.head_dim)
         return {"len": 0, "k": [torch.empty(shape, dtype=torch.bfloat16, device=self.device) for _ in self.layers],
-                "v": [torch.empty(shape, dtype=torch.bfloat16, device=self.device) for _ in self.layers]}
+                "v": [torch.empty(shape, dtype=torch.bfloat16, device=self.device) for _ in self.layers],
+                "err": torch.zeros(1, dtype=torch.int32, device=self.device)}
 
     def forward(self, inputs_embeds, key_valid=None, collect_routing=False, kv_cache=None):
         """inputs_embeds [B,S,d] bf16; key_valid uint8 [B,S] (1 = real token) or None.
@@ -313,6 +343,9 @@ class LlamaStack:
         needed_mask = nr[1] if (nr is not None and not collect_routing and kv_cache is None and nr[1].numel() == B * S) else None
         self.gate_pass += 1
         pos0 = kv_cache["len"] if kv_cache is not None else 0
+        if kv_cache is not None and pos0 + S > kv_cache["k"][0].shape[1]:
+            raise ValueError(f"LlamaStack.forward: positions {pos0}..{pos0 + S - 1} do not fit the KV cache of {kv_cache['k'][0].shape[1]} rows")
+        self.ensure_positions(pos0 + S)
         # a handful of rows (the single-token decode steps): the projections are weight streams -> GEMV kernel (HBM-bound)
         lin = (lambda a, w, **kw: ops.gemv(a, w, **kw)) if B * S <= 8 else (lambda a, w, **kw: ops.gemm(a, w, **kw))
         ff = cfg.intermediate_size
@@ -408,10 +441,10 @@ class LlamaStack:
         for i, lw in enumerate(self.layers):
             if fold:                                            # norm + projection + RoPE + cache append: one launch, the three launches' bits
                 qkv = ops.gemv_rmsnorm_rope_append(x, lw["ln1"], cfg.rms_norm_eps, lw["qkv"], self.cos, self.sin, kv_cache["k"][i],
-                                                   kv_cache["v"][i], counters[0:1], H, D)
+                                                   kv_cache["v"][i], counters[0:1], H, D, err=kv_cache["err"])
             else:
                 qkv = ops.gemv(ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps), lw["qkv"])
-                ops.decode_rope_append(qkv, self.cos, self.sin, kv_cache["k"][i], kv_cache["v"][i], counters[0:1], H, D)
+                ops.decode_rope_append(qkv, self.cos, self.sin, kv_cache["k"][i], kv_cache["v"][i], counters[0:1], H, D, err=kv_cache["err"])
             q4 = qkv.view(B, 1, 3, H, D)[:, :, 0]
             attn = ops.attention(q4, kv_cache["k"][i], kv_cache["v"][i], causal=False, sk_dev=counters[1:2])
             x = ops.gemv(attn.view(B, d), lw["o"], residual=x)

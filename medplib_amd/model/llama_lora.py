@@ -610,6 +610,7 @@ def forward_train(llm, embeds, key_valid):
     H, D = cfg.num_attention_heads, cfg.head_dim
     T = B * S
     x = embeds.reshape(T, d)
+    llm.ensure_positions(S)                                     # cos / sin / sin_neg past max_position_embeddings (HF 4.31 regrows its cache)
     lora.step += 1
     lora.p_active = lora.p if llm.training else 0.0
     lora.keep_bits = {}                                         # seed -> the mask bytes _adapter_down left for this step's backward
@@ -764,6 +765,7 @@ def backward(llm, saved, d_hidden, d_aux=None, need_d_embeds=True):
     H, D, d = cfg.num_attention_heads, cfg.head_dim, cfg.hidden_size
     T = B * S
     r = lora.r
+    llm.ensure_positions(S)                                     # (forward_train grew the tables already; a no-op then)
     grads = {}
 
     def take(i, ops_pad, dB, dAT):

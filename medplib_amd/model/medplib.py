@@ -747,7 +747,12 @@ class MedPLIBForCausalLM(nn.Module):
                 graph.replay()                                   # feeds token i-1, produces token i
                 hid_all[i - 1:i].copy_(h_static.view(1, d))
                 toks[i:i + 1].copy_(tok)
-            got = toks[:upto].cpu().tolist()                     # the only host synchronisation of the loop
+            # the only host synchronisation of the loop: the ids and the cache's error word (MP_POS_ERR_*) in one copy
+            got = torch.cat([toks[:upto], cache["err"].to(torch.int64)]).cpu().tolist()
+            err = got.pop()
+            if err:
+                raise RuntimeError(f"_decode_graph: decode steps {n}..{upto - 1} (positions {S + n - 1}..{S + upto - 2}) ran past the RoPE table "
+                                   f"({llm.cos.shape[0]} rows) or the KV cache ({cache['k'][0].shape[1]} rows): error word {err}")
             n = upto
             if eos_token_id in got:
                 n = got.index(eos_token_id) + 1
@@ -797,6 +802,9 @@ class MedPLIBForCausalLM(nn.Module):
                 h, _, _ = m.llm.forward(emb.view(1, 1, -1), None, kv_cache=cache)
                 step_hiddens.append(h)
                 last = h[0, -1:]
+            err = int(cache["err"][0])
+            if err:
+                raise RuntimeError(f"_greedy: a decode step ran past the RoPE table or the KV cache: error word {err}")
         return np.concatenate([ids, np.asarray(generated, dtype=np.int64)[None]], 1), [hidden] + step_hiddens
 
     @torch.no_grad()

@@ -280,16 +280,20 @@ def gemv_rmsnorm(x, norm_w, eps, w, out_dtype=torch.bfloat16, act=ACT_NONE):
     return out
 
 
-def gemv_rmsnorm_rope_append(x, norm_w, eps, w_qkv, cos_t, sin_t, cache_k, cache_v, pos_dev, heads, head_dim):
+def gemv_rmsnorm_rope_append(x, norm_w, eps, w_qkv, cos_t, sin_t, cache_k, cache_v, pos_dev, heads, head_dim, err=None):
     """One decode-step launch for input_layernorm -> q|k|v projection -> RoPE at pos_dev[0] -> KV-cache append (bit-identical with
-    rmsnorm + gemv + decode_rope_append).  Returns qkv [M, 3*H*D] of which only the q third is written (the rotated q)."""
+    rmsnorm + gemv + decode_rope_append).  Returns qkv [M, 3*H*D] of which only the q third is written (the rotated q).
+    Bounded on the device (mp_gemv_rmsnorm_rope_append_bounded_bf16): a position past the table or the cache writes nothing and ORs
+    MP_POS_ERR_* into `err` (int32 [1] on the device: the KV cache's "err" word; None = a fresh word nobody reads)."""
     _chk(x, torch.bfloat16, "gemv_rmsnorm_rope.x"); _chk(w_qkv, torch.bfloat16, "gemv_rmsnorm_rope.w"); _chk(pos_dev, torch.int32, "gemv_rmsnorm_rope.pos")
     M, K = x.shape
     assert w_qkv.shape == (3 * heads * head_dim, K) and x.stride(1) == 1 and w_qkv.stride(1) == 1
     assert cache_k.stride(3) == 1 and cache_k.stride(2) == head_dim and cache_v.stride() == cache_k.stride()
     qkv = torch.empty((M, 3 * heads * head_dim), dtype=torch.bfloat16, device=x.device)
-    lib().call("mp_gemv_rmsnorm_rope_append_bf16", _p(x), x.stride(0), _p(norm_w), float(eps), _p(w_qkv), w_qkv.stride(0), _p(qkv), qkv.stride(0),
-               _p(cos_t), _p(sin_t), _p(cache_k), _p(cache_v), _p(pos_dev), M, heads, head_dim, K, cache_k.stride(0), cache_k.stride(1), _stream())
+    table_rows, cache_rows, err = _decode_bounds(cos_t, sin_t, cache_k, cache_v, err)
+    lib().call("mp_gemv_rmsnorm_rope_append_bounded_bf16", _p(x), x.stride(0), _p(norm_w), float(eps), _p(w_qkv), w_qkv.stride(0), _p(qkv),
+               qkv.stride(0), _p(cos_t), _p(sin_t), _p(cache_k), _p(cache_v), _p(pos_dev), M, heads, head_dim, K, cache_k.stride(0),
+               cache_k.stride(1), table_rows, cache_rows, _p(err), _stream())
     return qkv
 
 
@@ -405,6 +409,8 @@ def attention_bwd(q, k, v, out, d_out, lse2, causal=True, key_valid=None, scale=
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     assert Sq == Sk, "self-attention backward (the fused dqkv buffer holds one row per position)"
+    if rope is not None and min(rope[0].shape[0], rope[1].shape[0]) < Sq:
+        raise ValueError(f"attention_bwd: the RoPE tables have {min(rope[0].shape[0], rope[1].shape[0])} rows, positions need {Sq}")
     _chk(d_out, torch.bfloat16, "attention_bwd.d_out"); _chk(out, torch.bfloat16, "attention_bwd.out")
     assert d_out.stride(2) == 1 and out.stride(2) == 1
     delta = torch.empty((B * H, Sq), dtype=torch.float32, device=q.device)
@@ -735,13 +741,25 @@ def dropout_bf16(x, p, seed):
     return y
 
 
-def decode_rope_append(qkv, cos_t, sin_t, cache_k, cache_v, pos_dev, heads, head_dim):
+def _decode_bounds(cos_t, sin_t, cache_k, cache_v, err):
+    """(table_rows, cache_rows, err word) for the bounded decode entry points."""
+    _chk(cos_t, torch.float32, "decode.cos"); _chk(sin_t, torch.float32, "decode.sin")
+    assert cos_t.dim() == 2 and sin_t.shape == cos_t.shape and cache_v.shape == cache_k.shape
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=cache_k.device)
+    _chk(err, torch.int32, "decode.err")
+    return cos_t.shape[0], cache_k.shape[1], err
+
+
+def decode_rope_append(qkv, cos_t, sin_t, cache_k, cache_v, pos_dev, heads, head_dim, err=None):
     """qkv [B, 3*H*D] (one new token per sequence): q rotated in place, rotated k / v written to the caches [B, max_len, H, D] at
-    position pos_dev[0] (int32 on the device)."""
+    position pos_dev[0] (int32 on the device).  Bounded on the device (mp_decode_rope_append_bounded_bf16): a position past the table
+    or the cache writes nothing and ORs MP_POS_ERR_* into `err` (as gemv_rmsnorm_rope_append)."""
     _chk(qkv, torch.bfloat16, "decode_rope_append.qkv"); _chk(pos_dev, torch.int32, "decode_rope_append.pos")
     assert qkv.dim() == 2 and qkv.stride(1) == 1 and cache_k.stride(3) == 1 and cache_k.stride(2) == head_dim
-    lib().call("mp_decode_rope_append_bf16", _p(qkv), qkv.stride(0), _p(cos_t), _p(sin_t), _p(cache_k), _p(cache_v), _p(pos_dev), qkv.shape[0],
-               heads, head_dim, cache_k.stride(0), cache_k.stride(1), _stream())
+    table_rows, cache_rows, err = _decode_bounds(cos_t, sin_t, cache_k, cache_v, err)
+    lib().call("mp_decode_rope_append_bounded_bf16", _p(qkv), qkv.stride(0), _p(cos_t), _p(sin_t), _p(cache_k), _p(cache_v), _p(pos_dev),
+               qkv.shape[0], heads, head_dim, cache_k.stride(0), cache_k.stride(1), table_rows, cache_rows, _p(err), _stream())
 
 
 def advance_ints(t, delta=1):
@@ -770,12 +788,13 @@ def layernorm(x, w, b, eps, out=None):
 
 def rope_qk_(qkv, cos_t, sin_t, seq, heads, head_dim, pos_offset=0):
     """in place on a fused [tokens, 3*heads*head_dim] bf16 buffer; cos/sin fp32 [>=seq+pos_offset, head_dim/2]; token t of a
-    sequence gets position (t % seq) + pos_offset (pos_offset = cached length when decoding)."""
-    _chk(qkv, torch.bfloat16, "rope.qkv"); _chk(cos_t, torch.float32, "rope.cos")
+    sequence gets position (t % seq) + pos_offset (pos_offset = cached length when decoding).  Tables shorter than seq + pos_offset:
+    MedplibError from mp_rope_qk_bounded_bf16 (LlamaStack.ensure_positions grows them)."""
+    _chk(qkv, torch.bfloat16, "rope.qkv"); _chk(cos_t, torch.float32, "rope.cos"); _chk(sin_t, torch.float32, "rope.sin")
     assert qkv.dim() == 2 and qkv.stride(1) == 1 and cos_t.is_contiguous() and sin_t.is_contiguous()
-    assert cos_t.shape[0] >= seq + pos_offset and cos_t.shape[1] == head_dim // 2
-    lib().call("mp_rope_qk_bf16", _p(qkv), qkv.stride(0), _p(cos_t), _p(sin_t), qkv.shape[0], seq, heads, head_dim, int(pos_offset),
-               _stream())
+    assert cos_t.shape[1] == head_dim // 2 and sin_t.shape[1] == head_dim // 2
+    lib().call("mp_rope_qk_bounded_bf16", _p(qkv), qkv.stride(0), _p(cos_t), _p(sin_t), qkv.shape[0], seq, heads, head_dim, int(pos_offset),
+               min(cos_t.shape[0], sin_t.shape[0]), _stream())
     return qkv
 
 
@@ -809,23 +828,26 @@ def gemm_fold_ok(M, N, K):
 
 def gemm_qkv_rope(a, w_interleaved, cos_t, sin_t, seq, heads, head_dim, pos_offset=0, out=None, row_scale=None):
     """qkv = a @ W^T with RoPE applied to the q and k thirds in the GEMM epilogue; `w_interleaved` = rope_interleave_qkv(W).  The result
-    (standard [tokens, 3*H*D] layout) is bit-identical with gemm(a, W) followed by rope_qk_."""
+    (standard [tokens, 3*H*D] layout) is bit-identical with gemm(a, W) followed by rope_qk_.  Tables shorter than seq + pos_offset:
+    MedplibError from the bounded entry points."""
     _chk(a, torch.bfloat16, "gemm_qkv_rope.a"); _chk(w_interleaved, torch.bfloat16, "gemm_qkv_rope.w"); _chk(cos_t, torch.float32, "gemm_qkv_rope.cos")
+    _chk(sin_t, torch.float32, "gemm_qkv_rope.sin")
     M, K = a.shape
     N = w_interleaved.shape[0]
     assert a.stride(1) == 1 and w_interleaved.stride(1) == 1 and cos_t.is_contiguous() and sin_t.is_contiguous()
-    assert cos_t.shape[0] >= seq + pos_offset and cos_t.shape[1] == head_dim // 2 and N == 3 * heads * head_dim
+    assert cos_t.shape[1] == head_dim // 2 and sin_t.shape[1] == head_dim // 2 and N == 3 * heads * head_dim
+    table_rows = min(cos_t.shape[0], sin_t.shape[0])
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
     _ensure_gemm_workspace(a.device)
     t0 = GEMM_TIMER.begin() if GEMM_TIMER is not None else None
     if row_scale is not None:       # folded input norm: a = the raw residual stream, w carries the norm weight, row_scale = rstd [M] fp32
         _chk(row_scale, torch.float32, "gemm_qkv_rope.row_scale"); assert row_scale.is_contiguous() and row_scale.numel() == M
-        lib().call("mp_gemm_qkv_rope_scaled_bf16", _p(a), a.stride(0), _p(w_interleaved), w_interleaved.stride(0), _p(out), out.stride(0), _p(cos_t),
-                   _p(sin_t), _p(row_scale), M, N, K, int(seq), int(pos_offset), int(head_dim), _stream())
+        lib().call("mp_gemm_qkv_rope_scaled_bounded_bf16", _p(a), a.stride(0), _p(w_interleaved), w_interleaved.stride(0), _p(out), out.stride(0),
+                   _p(cos_t), _p(sin_t), _p(row_scale), M, N, K, int(seq), int(pos_offset), int(head_dim), table_rows, _stream())
     else:
-        lib().call("mp_gemm_qkv_rope_bf16", _p(a), a.stride(0), _p(w_interleaved), w_interleaved.stride(0), _p(out), out.stride(0), _p(cos_t),
-                   _p(sin_t), M, N, K, int(seq), int(pos_offset), int(head_dim), _stream())
+        lib().call("mp_gemm_qkv_rope_bounded_bf16", _p(a), a.stride(0), _p(w_interleaved), w_interleaved.stride(0), _p(out), out.stride(0),
+                   _p(cos_t), _p(sin_t), M, N, K, int(seq), int(pos_offset), int(head_dim), table_rows, _stream())
     if GEMM_TIMER is not None:
         GEMM_TIMER.end(2.0 * M * N * K, t0)
     return out
