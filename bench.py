@@ -13,6 +13,10 @@ Launch:  python bench.py --gpus N --steps K --warmup W          (N > 1 without a
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line.  The line never claims a GPU count other than the one asked for: `--gpus N` with WORLD_SIZE != N is
 refused, and `rccl_ranks` is what the RCCL communicator itself reports (ncclCommCount through the C ABI's mp_comm_count).
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` and prints the line: the headline and what the timed steps
+themselves recorded (`roofline` from their sampled GEMM launches, `dp_bucket`, `mask_tail`).  `--full` adds everything that takes work of
+its own after the timed steps: the unshared `roofline` steps and their PMC `traffic` passes, `roofline_upsampler`, `lora_stage3`, `configs`,
+`decode`, `cpu_baseline` and `parity` (the process exits 3 when `parity` violates its bounds).
 `--dry` runs the launch / rendezvous / timing / one-line protocol on CPU ranks over gloo with a stand-in gradient bucket (no GPU,
 no model): what tests/test_bench_launch.py drives.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy,
 so that two builds can be compared output for output."""
@@ -387,7 +391,7 @@ def upsampler_roofline(device):
 def lora_secondary(args, device, ds_config, synthetic_batch, rank, steps=8, warmup=3, secondary=None):
     """Secondary object of the default line: scripts/train_stage3.sh's configuration (the one every shipped script trains: dense Llama-7B,
     LoRA r = 8 / alpha 16 / dropout 0.05 on gate / up / down_proj, mask decoder + text_hidden_fcs trainable) = the whole decoder backward in
-    the step, measured in the same process after the headline leg (8 steps after 3) so the driver's run carries it."""
+    the step, measured in the same process after the headline leg (8 steps after 3) so a `--full` run carries it."""
     from medplib_amd import engine
     from medplib_amd.model.config import MedPLIBConfig
     from medplib_amd.model.medplib import LISAForCausalLM
@@ -591,6 +595,10 @@ def main():
                     help="secondary line: scripts/train_stage3.sh's configuration (dense Llama-7B, LoRA r = 8 / alpha 16 / dropout 0.05 on "
                          "gate/up/down_proj, mask decoder + text_hidden_fcs trainable) = the whole decoder backward in the step; the "
                          "contract's default line is BASELINE configs[3] (LoRA off)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what takes work of its own: the unshared `roofline` steps and their PMC "
+                         "`traffic` passes, `roofline_upsampler`, `lora_stage3`, `configs`, `decode`, `cpu_baseline` and `parity`.  A plain run "
+                         "does the headline only; the --no-* switches below thin out a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-lora-line", action="store_true", help="skip the secondary LoRA measurement (`lora_stage3`) of the default line")
     ap.add_argument("--no-secondary", action="store_true", help="skip the `configs` (BASELINE configs[1], [2], [4] forwards) and `decode` objects of the default line")
@@ -602,9 +610,10 @@ def main():
     ap.add_argument("--towers-in-order", action="store_true",
                     help="debug / A-B: the frozen CLIP tower of a step queues behind the previous step's decoder instead of starting on its own "
                          "stream when the step is issued (model.towers_run_ahead, the default since round 3: +2.6 %% samples/s)")
-    ap.add_argument("--roofline-steps", type=int, default=6,
+    ap.add_argument("--roofline-steps", type=int, default=None,
                     help="extra un-timed steps AFTER the timed region in which the dominant GEMM is measured unshared (towers in order, SAM "
-                         "encoder and mask tail on the decoder's stream): `roofline`; the timed region's own figure is `roofline_timed_region`")
+                         "encoder and mask tail on the decoder's stream): `roofline`; the timed region's own figure is `roofline_timed_region`.  "
+                         "Default 6 with --full, else 0 (`roofline` is then the timed region's figure)")
     ap.add_argument("--no-side-streams", action="store_true",
                     help="debug only: SAM encoder and mask tail on the decoder's stream (what the side streams buy; what they cost the GEMM launches they run beside)")
     ap.add_argument("--host-inputs", action="store_true",
@@ -624,6 +633,10 @@ def main():
                          "seeded sample when it is larger than 8 M elements); with --dry the reduced gradient bucket.  The inputs and weights are "
                          "seeded, so two runs with the same arguments compare output for output")
     args = ap.parse_args()
+    if not args.full:                 # a plain run: nothing after the timed steps but --dump-outputs and the line
+        args.no_cpu_baseline = args.no_lora_line = args.no_secondary = args.no_live_traffic = True
+    if args.roofline_steps is None:
+        args.roofline_steps = 6 if args.full else 0
     if args.ep and args.gpus % args.ep:
         sys.exit(f"bench.py: --ep {args.ep} does not divide --gpus {args.gpus}")
     if args.ep and "--batch" not in " ".join(sys.argv):
@@ -1013,7 +1026,7 @@ def gpu_main(args, emit):
         if ep_obj is not None:
             res["ep"] = ep_obj
         print(f"[bench] gpu leg: {value:.2f} samples/s, {dt / args.steps * 1e3:.1f} ms/step", file=sys.stderr, flush=True)
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 model.sync_side_streams()
                 torch.cuda.synchronize()

@@ -2,10 +2,10 @@
 # round 6 closing run: the driver's bench command, kernel table + CU x time + PMC passes of the headline step, LoRA kernel table, decode timelines
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; mkdir -p gpurun_out
 tag=${1:-r06}
-python bench.py --steps 20 --warmup 5 > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err; echo "bench rc=$?"
+python bench.py --full --steps 20 --warmup 5 > profiles/${tag}_bench.json; echo "bench rc=$?"
 python - <<PY
 import json
-d=json.loads(open("gpurun_out/${tag}_bench.json").read().strip().splitlines()[-1])
+d=json.loads(open("profiles/${tag}_bench.json").read().strip().splitlines()[-1])
 r=d["roofline"]
 print("headline", d["ms_per_step"], "value", d["value"], "host", d.get("host_issue_ms_per_step"), "frac", r["frac"], "clk", r.get("effective_clock_ghz"), r.get("frac_at_effective_clock"), "traffic", r.get("traffic"))
 l=d.get("lora_stage3") or {}
