@@ -683,7 +683,6 @@ int launch_attn2(const AttnArgs& a, hipStream_t stream) {
 // p * V.  Every split leaves (max, sum, unnormalised o[D]) in the workspace, takes a ticket, and the last arriver of the head
 // merges the NS partials in split order.  fp32 throughout, P rounded to bf16 before the PV product like the tiled kernels.
 // Workspace / tickets: the registered split-K scratch of the GEMM (mp_gemm_set_workspace); without it NS = 1.
-void mp_gemm_split_workspace(hipStream_t stream, float** ws, int** tickets, int64_t* bytes);
 
 namespace {
 

@@ -30,6 +30,10 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 extern "C" const char* mp_last_error_string();
 void mp_set_error(const char* fmt, ...);
 int mp_check_launch(const char* what);
+// what the rest of the library shares with the bf16 GEMM (gemm_dispatch.cpp): the CU count of the current device (cached per device), and the
+// split-K scratch registered for `stream` with mp_gemm_set_workspace / mp_gemm_set_stream_workspace (null and 0 when there is none)
+int mp_device_cus();
+void mp_gemm_split_workspace(hipStream_t stream, float** ws, int** tickets, int64_t* bytes);
 
 #define MP_REQUIRE(cond, code, ...)        \
   do {                                     \

@@ -36,9 +36,6 @@
 #include "gemm_common.h"
 #include <stdlib.h>
 #include <algorithm>
-#include <map>
-#include <mutex>
-#include <utility>
 
 namespace {
 
@@ -641,71 +638,6 @@ __global__ __launch_bounds__(NT2, 1) void gemm256v3_bf16_nt_kernel(GemmArgs g) {
 
 
 }  // namespace
-
-// split-K workspaces, registered by the host: >= n_cu * 256 KiB of fp32 partials + >= 384 tickets each (the 320-row kernel keeps three words per tail tile).  One workspace serves
-// one stream at a time, so a stream that runs GEMMs concurrently with others registers its own (mp_gemm_set_stream_workspace);
-// launches on any other stream of that device use the device's default entry (mp_gemm_set_workspace).  The table is keyed by
-// (device, stream) with no cap on either; it is only a directory of caller-owned buffers (the library never allocates).
-struct SplitWs { float* ws; int* tickets; int64_t bytes; };
-static std::mutex g_split_mu;
-static std::map<std::pair<int, hipStream_t>, SplitWs> g_split;          // stream == nullptr: the device's default entry
-
-static int current_device() {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  return dev;
-}
-
-static int register_split_ws(hipStream_t stream, void* ws, int64_t ws_bytes, int* tickets) {
-  std::lock_guard<std::mutex> lk(g_split_mu);
-  const auto key = std::make_pair(current_device(), stream);
-  if (ws) g_split[key] = SplitWs{(float*)ws, tickets, ws_bytes};
-  else g_split.erase(key);
-  return MP_OK;
-}
-
-extern "C" int mp_gemm_set_workspace(void* ws, int64_t ws_bytes, int* tickets, int n_tickets) {
-  MP_REQUIRE(ws == nullptr || (tickets != nullptr && n_tickets >= 384), MP_ERR_ARG, "mp_gemm_set_workspace: need >= 384 zeroed int tickets");
-  return register_split_ws(nullptr, ws, ws_bytes, tickets);
-}
-
-extern "C" int mp_gemm_set_stream_workspace(hipStream_t stream, void* ws, int64_t ws_bytes, int* tickets, int n_tickets) {
-  MP_REQUIRE(ws == nullptr || (tickets != nullptr && n_tickets >= 384), MP_ERR_ARG, "mp_gemm_set_stream_workspace: need >= 384 zeroed int tickets");
-  MP_REQUIRE(stream != nullptr, MP_ERR_ARG, "mp_gemm_set_stream_workspace: the default entry is mp_gemm_set_workspace");
-  return register_split_ws(stream, ws, ws_bytes, tickets);
-}
-
-void mp_gemm_split_workspace(hipStream_t stream, float** ws, int** tickets, int64_t* bytes) {
-  std::lock_guard<std::mutex> lk(g_split_mu);
-  const int dev = current_device();
-  auto it = g_split.find(std::make_pair(dev, stream));
-  if (it == g_split.end()) it = g_split.find(std::make_pair(dev, (hipStream_t) nullptr));
-  if (it == g_split.end()) { *ws = nullptr; *tickets = nullptr; *bytes = 0; return; }
-  *ws = it->second.ws; *tickets = it->second.tickets; *bytes = it->second.bytes;
-}
-
-// Whether `stream` has its own registered workspace, i.e. the host declared that it runs GEMMs CONCURRENTLY with the device's primary
-// stream.  The 320-row kernel's cooperative tail (units that WAIT for their siblings) is only deadlock-free while a single kernel on
-// the device waits at a time: two such kernels on two streams can each hold CUs the other's missing units need.
-bool mp_gemm_stream_registered(hipStream_t stream) {
-  if (!stream) return false;
-  std::lock_guard<std::mutex> lk(g_split_mu);
-  return g_split.find(std::make_pair(current_device(), stream)) != g_split.end();
-}
-
-// CU count of the CURRENT device (immutable per device; cached per device id, not in a process-wide static)
-int mp_device_cus() {
-  static std::mutex mu;
-  static std::map<int, int> cus;
-  const int dev = current_device();
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cus.find(dev);
-  if (it != cus.end()) return it->second;
-  int n = 0;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  cus[dev] = n;
-  return n;
-}
 
 int mp_launch_gemm256(const GemmArgs& g, int batch, hipStream_t stream) {
   static int abl = -1;

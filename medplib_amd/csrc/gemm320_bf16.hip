@@ -3,7 +3,7 @@
 // tiles = 320 tiles = 1.25 waves on 256 CUs for every N = 4096 projection (o_proj, down_proj, three of the four dgrad GEMMs of LoRA training),
 // 3.75 waves for qkv; 16 row tiles of 320 make that exactly 1 and 3 waves of 1.25 x the work each, without the split-K tail's fp32
 // partials going through memory (64 MB written + 48 MB read per N = 4096 launch).  mp_gemm_bf16_nt picks this kernel per call from the
-// two wave counts (use_320 in gemm_bf16.hip).
+// two wave counts (use_320 in gemm_dispatch.cpp).
 //
 // 512 threads = 8 waves as 4 (M) x 2 (N); a wave owns an 80 x 128 output tile = 5 x 8 fragments of v_mfma_f32_16x16x32_bf16 (160
 // accumulator registers).  LDS: 2 stages x (A 40 KiB + B 32 KiB) = 144 KiB, one workgroup per CU, two waves per SIMD.  The two N halves
@@ -26,7 +26,7 @@
 // at one wave of tiles (scripts/gemm_ksweep.py) showed 35 us of fixed cost per launch, 28 of them the epilogue (K = 128: 38.1 us with, 10.8
 // without it); each family alone compiles to 241-253 VGPRs with no spill and the fixed cost is 10 us -- below the 256x256 kernel's 14.
 // The kernel then beat the 256-row tiling on every dense decoder shape (o_proj 131 vs 180 us, down 301 vs 362, qkv+RoPE 355 vs 383, CLIP
-// fc1 43.5 vs 72 on the 128x128 kernel), so the selection model in gemm_bf16.hip was recalibrated from the K sweeps.
+// fc1 43.5 vs 72 on the 128x128 kernel), so the selection model (now in gemm_dispatch.cpp) was recalibrated from the K sweeps.
 // Batched expert calls too: flat tile decode over the experts' device-side row counts, the MoE dispatch folded into the A fetch (one
 // 32-bit lane offset per DMA piece instead of one per operand: 5 registers), SwiGLU pairing and the combine scatter as epilogue families,
 // and the 256x256 kernel's tail split-K (batched calls only; dense calls keep whole waves and one accumulation order per shape).
@@ -34,12 +34,6 @@
 #include "gemm_common.h"
 #include <stdlib.h>
 #include <algorithm>
-
-int mp_device_cus();
-void mp_gemm_split_workspace(hipStream_t stream, float** ws, int** tickets, int64_t* bytes);
-bool mp_gemm_stream_registered(hipStream_t stream);
-bool mp_gemm_policy_whole_tiles();
-long long mp_gemm_tail_wait_value();
 
 namespace {
 
@@ -589,7 +583,7 @@ __global__ __launch_bounds__(NT3, 1) void gemm320_bf16_nt_kernel(GemmArgs g) {
 }  // namespace
 
 // Whether the 320-row tiling is eligible for this call (dense bf16-out, aligned, offsets fit 32 bits) -- the choice between the two
-// tilings is use_320() in gemm_bf16.hip.
+// tilings is use_320() in gemm_dispatch.cpp.
 bool mp_gemm320_eligible(const GemmArgs& g, int batch) {
   if (batch < 1 || batch > MAX_FLAT_BATCH3 || g.out_f32) return false;
   if (g.keep_gu && (batch != 1 || (g.ld_gu & 7) || (reinterpret_cast<uintptr_t>(g.keep_gu) & 15))) return false;
@@ -616,7 +610,7 @@ bool mp_gemm320_eligible(const GemmArgs& g, int batch) {
 // Round 6, late: a DENSE call of at most half a wave of tiles (116 <= tiles <= 128 at 256 CUs: the N = 4096 projections at 2556 rows = BASELINE configs[1],
 // the dense VQA forward at batch 4: o_proj and down_proj are 8 x 16 = 128 tiles) may cut every tile in two or three along K with the cooperative
 // fix-up, instead of holding half the CUs for a whole tile-time (or 160 of them on 256-row tiles).  One rule for the selection model
-// (use_320, gemm_bf16.hip) and the launcher.  K >= 8192 only (the fix-up's 2 x 84 MB of partials cost ~25 us whatever K is), M >= 1024 (a tile row
+// (use_320, gemm_dispatch.cpp) and the launcher.  K >= 8192 only (the fix-up's 2 x 84 MB of partials cost ~25 us whatever K is), M >= 1024 (a tile row
 // mostly valid), never for the families that cannot split.  MP_GEMM320_SUBWAVE=0: off (A/B).  Returns the split factor (1: no split).
 int mp_gemm320_subwave_split(const GemmArgs& g, int batch) {
   static int on = -1;

@@ -1,5 +1,5 @@
-// Shared argument block and epilogue helpers of the bf16 MFMA GEMM kernels (gemm_bf16.hip: 128x128 tiles,
-// gemm256_bf16.hip: 256x256 ping-pong tiles).
+// Shared argument block and epilogue helpers of the three bf16 MFMA GEMM kernels (gemm_bf16.hip: 128x128 tiles, gemm256_bf16.hip: 256x256
+// ping-pong tiles, gemm320_bf16.hip: 320x256 tiles), and the host functions they and the selection / dispatch code (gemm_dispatch.cpp) share.
 #pragma once
 #include "common.h"
 
@@ -78,8 +78,20 @@ static __device__ __forceinline__ float apply_act(float v, int act) {
 }
 
 
-// implemented in gemm256_bf16.hip
+// The launchers, one per kernel file.  The 256 and 320 launchers check their own launch; mp_launch_gemm128 leaves that to the caller, and splits
+// along K only with may_split.
+void mp_launch_gemm128(const GemmArgs& g, int batch, bool may_split, hipStream_t stream);
 int mp_launch_gemm256(const GemmArgs& g, int batch, hipStream_t stream);
+int mp_launch_gemm320(const GemmArgs& g, int batch, hipStream_t stream);
+// gemm320_bf16.hip: whether the 320-row kernel takes the call at all, and the K split factor of a dense half-wave call (1 = none)
+bool mp_gemm320_eligible(const GemmArgs& g, int batch);
+int mp_gemm320_subwave_split(const GemmArgs& g, int batch);
+// gemm_dispatch.cpp (beside mp_device_cus and mp_gemm_split_workspace in common.h): whether `stream` registered a split-K scratch of its own,
+// MP_GEMM_VARIANT, tile policy 3 (tails never split) and the split tail's wait in shader cycles
+bool mp_gemm_stream_registered(hipStream_t stream);
+int mp_gemm_variant();
+bool mp_gemm_policy_whole_tiles();
+long long mp_gemm_tail_wait_value();
 
 // Two neighbouring fragments' bf16x4 row pieces (fragment j: columns j*16 + fq*4 .. +3, fragment j+1: 16 columns further) become one
 // 16-byte piece per lane: v_permlane16_swap exchanges the odd 16-lane rows of the first operand with the even rows of the second (lane

@@ -15,8 +15,6 @@
 #include <stdlib.h>
 #include "gemm_common.h"
 
-int mp_device_cus();            // gemm256_bf16.hip (cached per device)
-
 namespace {
 
 constexpr int RB_THREADS = 256, RB_MAXC = 4;

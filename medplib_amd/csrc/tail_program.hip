@@ -19,8 +19,6 @@
 // the launch (no trap); the host reads sync[1] back and falls back to the op-by-op tail.
 #include "common.h"
 
-int mp_device_cus();            // gemm256_bf16.hip (cached per device)
-
 namespace {
 
 enum { OP_GEMM = 1, OP_REDUCE = 2, OP_LN_FWD = 3, OP_LN_BWD = 4, OP_ATTN_FWD = 5, OP_ATTN_BWD = 6, OP_COPY2D = 7 };

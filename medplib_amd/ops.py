@@ -161,6 +161,16 @@ def register_stream_workspace(stream):
         _STREAM_WS[key] = (ws, tickets)
 
 
+def _gemm_call(device, name, args, work, **timer_kw):
+    """One bf16 GEMM entry point of the library: the split-K scratch registered, the call bracketed by GEMM_TIMER when bench.py set one
+    (work = the launch's flop; timer_kw: KernelTimer.end's device-side row counts)."""
+    _ensure_gemm_workspace(device)
+    t0 = GEMM_TIMER.begin() if GEMM_TIMER is not None else None
+    lib().call(name, *args)
+    if GEMM_TIMER is not None:
+        GEMM_TIMER.end(work, t0, **timer_kw)
+
+
 def gemm(a, w, bias=None, residual=None, act=ACT_NONE, out_dtype=torch.bfloat16, out=None, alpha=1.0, m_dev=None):
     """out[M,N] = act(alpha * a[M,K] @ w[N,K]^T + bias) + residual.  a/w bf16 with unit inner stride."""
     _chk(a, torch.bfloat16, "gemm.a"); _chk(w, torch.bfloat16, "gemm.w")
@@ -175,13 +185,9 @@ def gemm(a, w, bias=None, residual=None, act=ACT_NONE, out_dtype=torch.bfloat16,
         _chk(bias, torch.float32, "gemm.bias")
     if residual is not None:
         _chk(residual, torch.bfloat16, "gemm.residual"); assert residual.stride(1) == 1
-    _ensure_gemm_workspace(a.device)
-    t0 = GEMM_TIMER.begin() if GEMM_TIMER is not None else None
-    lib().call("mp_gemm_bf16_nt", _p(a), a.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), _p(bias), _p(residual),
-               residual.stride(0) if residual is not None else 0, M, N, K, act, _dt(out.dtype), float(alpha), _p(m_dev),
-               _stream())
-    if GEMM_TIMER is not None:
-        GEMM_TIMER.end(2.0 * M * N * K, t0)
+    _gemm_call(a.device, "mp_gemm_bf16_nt", (_p(a), a.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), _p(bias), _p(residual),
+                                             residual.stride(0) if residual is not None else 0, M, N, K, act, _dt(out.dtype), float(alpha),
+                                             _p(m_dev), _stream()), 2.0 * M * N * K)
     return out
 
 
@@ -194,11 +200,8 @@ def gemm_swiglu_keep(a, w, act_out=None):
     act = torch.empty((M, N // 2), dtype=torch.bfloat16, device=a.device) if act_out is None else act_out
     gu = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
     assert act.shape == (M, N // 2) and act.stride(1) == 1
-    _ensure_gemm_workspace(a.device)
-    t0 = GEMM_TIMER.begin() if GEMM_TIMER is not None else None
-    lib().call("mp_gemm_swiglu_keep_bf16", _p(a), a.stride(0), _p(w), w.stride(0), _p(act), act.stride(0), _p(gu), gu.stride(0), M, N, K, _stream())
-    if GEMM_TIMER is not None:
-        GEMM_TIMER.end(2.0 * M * N * K, t0)
+    _gemm_call(a.device, "mp_gemm_swiglu_keep_bf16", (_p(a), a.stride(0), _p(w), w.stride(0), _p(act), act.stride(0), _p(gu), gu.stride(0), M, N, K,
+                                                      _stream()), 2.0 * M * N * K)
     return act, gu
 
 
@@ -332,14 +335,11 @@ def gemm_batched(a, w, out, m_dev=None, bias=None, act=ACT_NONE):
     E, M, K = a.shape
     N = w.shape[1]
     assert a.stride(2) == 1 and w.stride(2) == 1 and out.stride(2) == 1
-    _ensure_gemm_workspace(a.device)
-    t0 = GEMM_TIMER.begin() if GEMM_TIMER is not None else None
-    lib().call("mp_gemm_bf16_nt_batched", _p(a), a.stride(1), a.stride(0), _p(w), w.stride(1), w.stride(0), _p(out),
-               out.stride(1), out.stride(0), _p(bias), bias.stride(0) if bias is not None else 0, E, M, N, K, act,
-               _dt(out.dtype), _p(m_dev), _stream())
-    if GEMM_TIMER is not None:
-        # algorithmic rows = the rows the kernel processes: the device-side counts (read back after the region), else every slab row
-        GEMM_TIMER.end(2.0 * E * M * N * K, t0, rows_dev=m_dev, slab_rows=M, flop_per_row=2.0 * N * K)
+    # algorithmic rows = the rows the kernel processes: the device-side counts (read back after the region), else every slab row
+    _gemm_call(a.device, "mp_gemm_bf16_nt_batched", (_p(a), a.stride(1), a.stride(0), _p(w), w.stride(1), w.stride(0), _p(out), out.stride(1),
+                                                     out.stride(0), _p(bias), bias.stride(0) if bias is not None else 0, E, M, N, K, act,
+                                                     _dt(out.dtype), _p(m_dev), _stream()),
+               2.0 * E * M * N * K, rows_dev=m_dev, slab_rows=M, flop_per_row=2.0 * N * K)
     return out
 
 
@@ -839,17 +839,12 @@ def gemm_qkv_rope(a, w_interleaved, cos_t, sin_t, seq, heads, head_dim, pos_offs
     table_rows = min(cos_t.shape[0], sin_t.shape[0])
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
-    _ensure_gemm_workspace(a.device)
-    t0 = GEMM_TIMER.begin() if GEMM_TIMER is not None else None
+    name, scale = "mp_gemm_qkv_rope_bounded_bf16", ()
     if row_scale is not None:       # folded input norm: a = the raw residual stream, w carries the norm weight, row_scale = rstd [M] fp32
         _chk(row_scale, torch.float32, "gemm_qkv_rope.row_scale"); assert row_scale.is_contiguous() and row_scale.numel() == M
-        lib().call("mp_gemm_qkv_rope_scaled_bounded_bf16", _p(a), a.stride(0), _p(w_interleaved), w_interleaved.stride(0), _p(out), out.stride(0),
-                   _p(cos_t), _p(sin_t), _p(row_scale), M, N, K, int(seq), int(pos_offset), int(head_dim), table_rows, _stream())
-    else:
-        lib().call("mp_gemm_qkv_rope_bounded_bf16", _p(a), a.stride(0), _p(w_interleaved), w_interleaved.stride(0), _p(out), out.stride(0),
-                   _p(cos_t), _p(sin_t), M, N, K, int(seq), int(pos_offset), int(head_dim), table_rows, _stream())
-    if GEMM_TIMER is not None:
-        GEMM_TIMER.end(2.0 * M * N * K, t0)
+        name, scale = "mp_gemm_qkv_rope_scaled_bounded_bf16", (_p(row_scale),)
+    _gemm_call(a.device, name, (_p(a), a.stride(0), _p(w_interleaved), w_interleaved.stride(0), _p(out), out.stride(0), _p(cos_t), _p(sin_t), *scale,
+                                M, N, K, int(seq), int(pos_offset), int(head_dim), table_rows, _stream()), 2.0 * M * N * K)
     return out
 
 
@@ -1595,19 +1590,16 @@ def gemm_batched_rows(a, w, out, m_dev, a_rows=None, c_rows=None, c_scale=None, 
     M = int(rows_stride) if a_rows is not None else a.shape[1]          # rows per expert slab (the capacity)
     lda, sa = (a.stride(0), 0) if a_rows is not None else (a.stride(1), a.stride(0))
     ldc, sc = (out.stride(0), 0) if c_rows is not None else (out.stride(1), out.stride(0))
-    _ensure_gemm_workspace(a.device)
-    t0 = GEMM_TIMER.begin() if GEMM_TIMER is not None else None
     if a_row_scale is not None:     # folded post-attention norm: a = the raw residual stream, w carries the norm weight, a_row_scale = rstd [tokens]
         assert a_rows is not None and c_rows is None and residual is None and act == ACT_SWIGLU_PAIR
         _chk(a_row_scale, torch.float32, "gemm_batched_rows.a_row_scale"); assert a_row_scale.numel() == a.shape[0]
-        lib().call("mp_gemm_bf16_nt_batched_rows_scaled", _p(a), lda, _p(a_rows), _p(a_row_scale), _p(w), w.stride(1), w.stride(0), _p(out), ldc, sc,
-                   int(rows_stride), E, int(M), N, K, _p(m_dev), _stream())
+        name, args = "mp_gemm_bf16_nt_batched_rows_scaled", (_p(a), lda, _p(a_rows), _p(a_row_scale), _p(w), w.stride(1), w.stride(0), _p(out), ldc, sc,
+                                                             int(rows_stride), E, int(M), N, K, _p(m_dev), _stream())
     else:
-        lib().call("mp_gemm_bf16_nt_batched_rows", _p(a), lda, sa, _p(a_rows), _p(w), w.stride(1), w.stride(0), _p(out), ldc, sc, _p(c_rows),
-                   _p(c_scale), _p(residual), residual.stride(0) if residual is not None else 0, int(rows_stride), E, int(M), N, K, act,
-                   _p(m_dev), _stream())
-    if GEMM_TIMER is not None:
-        GEMM_TIMER.end(2.0 * E * M * N * K, t0, rows_dev=m_dev, slab_rows=M, flop_per_row=2.0 * N * K)
+        name, args = "mp_gemm_bf16_nt_batched_rows", (_p(a), lda, sa, _p(a_rows), _p(w), w.stride(1), w.stride(0), _p(out), ldc, sc, _p(c_rows),
+                                                      _p(c_scale), _p(residual), residual.stride(0) if residual is not None else 0, int(rows_stride),
+                                                      E, int(M), N, K, act, _p(m_dev), _stream())
+    _gemm_call(a.device, name, args, 2.0 * E * M * N * K, rows_dev=m_dev, slab_rows=M, flop_per_row=2.0 * N * K)
     return out
 
 
