@@ -194,6 +194,16 @@ int mp_decode_rope_append_bounded_bf16(void* qkv, int64_t ld, const float* cos_t
 int mp_advance_ints(int* p, int n, int delta, hipStream_t stream);
 /* greedy next-token pick over fp32 logits (HF generate do_sample=False, MedPLIB.py:592-606). */
 int mp_argmax_rows_f32(const float* x, int64_t ld, int64_t rows, int cols, int64_t* out, hipStream_t stream);
+/* temperature sampling of the next token over fp32 logits (the serving worker's softmax(logits / T) + multinomial, model/serve/
+ * model_worker.py): per row w_j = exp((l_j - max l) * inv_temperature), out = the smallest i with w_i > 0 and sum_{j<=i} w_j > u * sum_j w_j
+ * (inverse CDF).  u [rows] fp32; out [rows] int64.  fp32 sums in a fixed order, no atomics: the same inputs give the same column on every
+ * launch, alone or beside other rows.  When no column qualifies (u >= 1, or within rounding of it) the pick is the last column with w > 0;
+ * never a column at or past `cols`, never one with w == 0 (a row without any: 0).  The uniforms of mp_gate_noise_f32 (gumbel = 0) are
+ * (k + 0.5) / 2^24 for a 24-bit k, evaluated in fp32: k + 0.5 is not representable from k = 2^23 up and rounds to the even neighbour, so the
+ * values lie in [2^-25, 1] and 1.0 itself is drawn with probability 2^-24 — never 0, but not strictly below 1: the rule above is what such a draw
+ * picks.  0 < cols <= 65536 and 0 < inv_temperature < inf, else MP_ERR_SHAPE before any launch; null operands MP_ERR_ARG. */
+int mp_sample_rows_f32(const float* logits, int64_t ld, int64_t rows, int cols, float inv_temperature, const float* u, int64_t* out,
+                       hipStream_t stream);
 /* out = silu(gu[:, :ff]) * gu[:, ff:]  (LlamaMLP). */
 int mp_swiglu_bf16(const void* gu, int64_t ldgu, void* out, int64_t ldo, int64_t rows, int ff, hipStream_t stream);
 int mp_cast_f32_to_bf16(const float* x, void* y, int64_t n, hipStream_t stream);

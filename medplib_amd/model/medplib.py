@@ -52,6 +52,32 @@ def _np_ids(t):
     return t.detach().cpu().numpy()
 
 
+def _argmax_pick(logits, step):
+    """The greedy next-token pick (HF do_sample=False).  `step` (the number of the generated token) is not used."""
+    return ops.argmax_rows(logits)
+
+
+class _SamplePick:
+    """The sampling next-token pick of generate_stream: token `step` of a request is ops.sample_rows at the uniform the keyed generator
+    draws under (seed, step).  `step` is an int (the first token, the token-by-token loop) or an int32 [1] device counter (the captured
+    decode step: every replay draws what the loop draws for that token).  An injected `uniforms(step) -> float` replaces the generator; it
+    runs on the host, so it cannot be captured.  last_u: the [1] tensor of the latest draw (inside a captured step: the graph's own buffer)."""
+    needs_step = True                        # the captured step keeps the number of the generated token on the device
+
+    def __init__(self, temperature, seed, device, uniforms=None):
+        self.temperature, self.seed, self.device, self.uniforms, self.last_u = float(temperature), int(seed), device, uniforms, None
+
+    def __call__(self, logits, step):
+        if self.uniforms is not None:
+            u = torch.tensor([float(self.uniforms(int(step)))], dtype=torch.float32, device=self.device)
+        elif torch.is_tensor(step):
+            u = ops.sample_uniform_dev(self.seed, step, self.device)
+        else:
+            u = ops.sample_uniform(self.seed, int(step), self.device)
+        self.last_u = u
+        return ops.sample_rows(logits, u, self.temperature)
+
+
 class _VisualModel(nn.Module):
     """`model.visual_model` (build_sam_vit_b, model/MedPLIB.py:141-150)."""
 
@@ -706,16 +732,22 @@ class MedPLIBForCausalLM(nn.Module):
         return {k: out10[i] for i, k in enumerate(LOSS_KEYS)}
 
 
-    def _decode_graph(self, prefill_hidden, cache, S, max_new_tokens, eos_token_id, check_every=16):
-        """Greedy decode with ONE captured HIP graph per call: embed(token) -> 32 decode layers (GEMV projections, RoPE + KV append
-        and attention at the device-side cache length) -> final norm -> lm_head -> argmax -> next token, all on the device; the host
-        replays the graph once per token (~450 kernel launches otherwise) and only looks at the generated ids every `check_every`
-        tokens to stop at EOS.  Tokens after the first EOS are discarded, so the result equals the token-by-token loop.
-        Returns (generated ids, [hidden of each fed token])."""
+    def _decode_graph(self, prefill_hidden, cache, S, max_new_tokens, stop_ids, looks=None, pick=_argmax_pick, debug=None, check_every=16):
+        """Decode with ONE captured HIP graph per call: embed(token) -> 32 decode layers (GEMV projections, RoPE + KV append
+        and attention at the device-side cache length) -> final norm -> lm_head -> pick (argmax, or the draw + sample_rows of a _SamplePick)
+        -> next token, all on the device; the host replays the graph once per token (~450 kernel launches otherwise) and only looks at the
+        generated ids when `looks` says so — the token counts at which it does, increasing and ending at max_new_tokens; by default every
+        `check_every` tokens — to stop at one of `stop_ids`.  Tokens after the first stop are discarded, so the result equals the
+        token-by-token loop.  A generator: at every look it yields (generated ids so far, stopped, [hidden of each fed token])."""
         cfg, dev, llm = self.config, self.device_, self.model.llm
         d = cfg.hidden_size
-        tok = ops.argmax_rows(llm.next_token_logits(prefill_hidden[0, -1:]))              # first generated token, int64 [1] on the device
-        counters = torch.tensor([S, S + 1], dtype=torch.int32, device=dev)
+        logits = llm.next_token_logits(prefill_hidden[0, -1:])
+        tok = pick(logits, 0)                                                             # first generated token, int64 [1] on the device
+        # [position of the fed token, keys after appending it] and, for a pick that draws, the number of the token being generated: one
+        # advance per replay bumps them all
+        needs_step = getattr(pick, "needs_step", False)
+        counters = torch.tensor([S, S + 1] + ([1] if needs_step else []), dtype=torch.int32, device=dev)
+        step_dev = counters[2:3] if needs_step else None
         toks = torch.empty(max_new_tokens, dtype=torch.int64, device=dev)
         hid_all = torch.empty((max_new_tokens, d), dtype=torch.bfloat16, device=dev)
         toks[0:1].copy_(tok)
@@ -724,12 +756,22 @@ class MedPLIBForCausalLM(nn.Module):
         # of token i pass pass0 + i, so the graph reads it from a device counter it advances itself
         pass0 = llm.gate_pass
         pass_dev = torch.tensor([pass0 + 1], dtype=torch.int32, device=dev)
+        n_dbg = len(debug) if debug is not None else 0
+        static = {}
+
+        def note(row, i):                    # debug (tests): the logits, the draw and the token of generated token i, read back at once
+            u = getattr(pick, "last_u", None)
+            debug.append((row[0].float().cpu(), None if u is None else float(u[0]), int(toks[i])))
+
+        if debug is not None:
+            note(logits, 0)
 
         def step():
             emb = ops.splice_rows(llm.embed_tokens, None, tok, d)
             h = llm.decode_step(emb.view(1, 1, d), cache, counters, pass_dev=pass_dev)
             h_static.copy_(h)
-            tok.copy_(ops.argmax_rows(llm.next_token_logits(h[0, -1:])))
+            static["logits"] = llm.next_token_logits(h[0, -1:])
+            tok.copy_(pick(static["logits"], step_dev))
             ops.advance_ints(counters, 1)
             ops.advance_ints(pass_dev, 1)
 
@@ -740,28 +782,36 @@ class MedPLIBForCausalLM(nn.Module):
             with torch.cuda.graph(graph, stream=side):
                 step()
         torch.cuda.current_stream().wait_stream(side)
+        if looks is None:
+            looks = list(range(1 + check_every, max_new_tokens, check_every)) + [max_new_tokens]
         n, done = 1, False
-        while n < max_new_tokens and not done:
-            upto = min(max_new_tokens, n + check_every)
-            for i in range(n, upto):
-                graph.replay()                                   # feeds token i-1, produces token i
-                hid_all[i - 1:i].copy_(h_static.view(1, d))
-                toks[i:i + 1].copy_(tok)
-            # the only host synchronisation of the loop: the ids and the cache's error word (MP_POS_ERR_*) in one copy
-            got = torch.cat([toks[:upto], cache["err"].to(torch.int64)]).cpu().tolist()
-            err = got.pop()
-            if err:
-                raise RuntimeError(f"_decode_graph: decode steps {n}..{upto - 1} (positions {S + n - 1}..{S + upto - 2}) ran past the RoPE table "
-                                   f"({llm.cos.shape[0]} rows) or the KV cache ({cache['k'][0].shape[1]} rows): error word {err}")
-            n = upto
-            if eos_token_id in got:
-                n = got.index(eos_token_id) + 1
-                done = True
-        generated = toks[:n].cpu().tolist()
-        step_hiddens = [hid_all[i:i + 1].view(1, 1, d) for i in range(n - 1)]
-        llm.gate_pass = pass0 + n - 1            # the passes the loop would have made (replays past the first EOS are discarded)
-        llm._draws_key = None                    # (the captured draw buffer belongs to the graph)
-        return generated, step_hiddens
+        try:
+            for upto in looks:
+                for i in range(n, upto):
+                    graph.replay()                                   # feeds token i-1, produces token i
+                    hid_all[i - 1:i].copy_(h_static.view(1, d))
+                    toks[i:i + 1].copy_(tok)
+                    if debug is not None:
+                        note(static["logits"], i)
+                # the only host synchronisation of the loop: the ids and the cache's error word (MP_POS_ERR_*) in one copy
+                got = torch.cat([toks[:upto], cache["err"].to(torch.int64)]).cpu().tolist()
+                err = got.pop()
+                if err:
+                    raise RuntimeError(f"_decode_graph: decode steps {n}..{upto - 1} (positions {S + n - 1}..{S + upto - 2}) ran past the RoPE table "
+                                       f"({llm.cos.shape[0]} rows) or the KV cache ({cache['k'][0].shape[1]} rows): error word {err}")
+                n = upto
+                hits = [i for i, t in enumerate(got) if t in stop_ids]
+                if hits:
+                    n = hits[0] + 1
+                    done = True
+                yield got[:n], done, [hid_all[i:i + 1].view(1, 1, d) for i in range(n - 1)]
+                if done:
+                    break
+        finally:                                 # (also when the consumer stops reading early)
+            llm.gate_pass = pass0 + n - 1        # the passes the loop would have made (replays past the first stop are discarded)
+            llm._draws_key = None                # (the captured draw buffer belongs to the graph)
+            if debug is not None:
+                del debug[n_dbg + n:]
 
     def _graph_decode_ok(self):
         """Whether _decode_graph computes what the token-by-token loop computes for this model: top-1, or top-2 on one rank without the
@@ -771,11 +821,13 @@ class MedPLIBForCausalLM(nn.Module):
             return True
         return cfg.top_k_experts == 2 and llm.ep is None and not cfg.use_residual and llm.rts_uniform_provider is None
 
-    def _greedy(self, ids, images_clip, max_new_tokens, eos_token_id, mask_images=None, image_token_types=None, image_token_lengths=None,
-                region_masks=None, valid_region_masks_bool=None):
-        """HF `generate(do_sample=False, use_cache=True)` on one sample (MedPLIB.py:592-606; prepare_inputs_for_generation,
-        medplib_moe_llama.py:451-485): prefill of the spliced prompt, then single-token decode steps against the KV cache.
-        Returns (output_ids [1, L + n] on the host, [hidden states of the prompt, of each fed token])."""
+    def _decode(self, ids, images_clip, max_new_tokens, stop_ids, mask_images=None, image_token_types=None, image_token_lengths=None,
+                region_masks=None, valid_region_masks_bool=None, pick=_argmax_pick, looks=None, host_pick=False, debug=None):
+        """Prefill of the spliced prompt, then single-token decode steps against the KV cache, the next token chosen by `pick` (the greedy
+        argmax unless told otherwise), until one of `stop_ids` or max_new_tokens.  Through the captured graph when the model allows it
+        (decode_with_graph, _graph_decode_ok(), more than two tokens) and the pick runs on the device (not host_pick), else token by token.
+        A generator of (generated ids so far, stopped, [hidden states of the prompt, of each fed token]): the graph path yields at `looks`
+        (_decode_graph), the loop after every token."""
         cfg, dev, m = self.config, self.device_, self.model
         plan, feats = self._encode_and_plan(ids, None, None, images_clip, mask_images, image_token_types, image_token_lengths,
                                             with_seg=False, region_masks=region_masks if region_masks else None,
@@ -785,27 +837,43 @@ class MedPLIBForCausalLM(nn.Module):
         embeds = ops.splice_rows(m.llm.embed_tokens, feats, src, cfg.hidden_size).view(1, S, cfg.hidden_size)
         cache = m.llm.new_kv_cache(1, S + max_new_tokens)
         hidden, _, _ = m.llm.forward(embeds, None, kv_cache=cache)
-        if self.decode_with_graph and max_new_tokens > 2 and self._graph_decode_ok():
+        if self.decode_with_graph and max_new_tokens > 2 and self._graph_decode_ok() and not host_pick:
             self.last_decode_path = "graph"
-            generated, step_hiddens = self._decode_graph(hidden, cache, S, max_new_tokens, eos_token_id)
-        else:
-            self.last_decode_path = "loop"
-            generated, step_hiddens = [], []
-            last = hidden[0, -1:]
-            for _ in range(max_new_tokens):
-                logits = m.llm.next_token_logits(last)
-                tok = int(ops.argmax_rows(logits)[0])
-                generated.append(tok)
-                if tok == eos_token_id or len(generated) == max_new_tokens:
-                    break
-                emb = ops.splice_rows(m.llm.embed_tokens, None, torch.tensor([tok], dtype=torch.int64, device=dev), cfg.hidden_size)
-                h, _, _ = m.llm.forward(emb.view(1, 1, -1), None, kv_cache=cache)
-                step_hiddens.append(h)
-                last = h[0, -1:]
-            err = int(cache["err"][0])
-            if err:
-                raise RuntimeError(f"_greedy: a decode step ran past the RoPE table or the KV cache: error word {err}")
-        return np.concatenate([ids, np.asarray(generated, dtype=np.int64)[None]], 1), [hidden] + step_hiddens
+            for generated, stopped, step_hiddens in self._decode_graph(hidden, cache, S, max_new_tokens, stop_ids, looks, pick, debug):
+                yield generated, stopped, [hidden] + step_hiddens
+            return
+        self.last_decode_path = "loop"
+        generated, hiddens = [], [hidden]
+        last = hidden[0, -1:]
+        for i in range(max_new_tokens):
+            logits = m.llm.next_token_logits(last)
+            tok = int(pick(logits, i)[0])
+            generated.append(tok)
+            if debug is not None:
+                u = getattr(pick, "last_u", None)
+                debug.append((logits[0].float().cpu(), None if u is None else float(u[0]), tok))
+            if tok in stop_ids or len(generated) == max_new_tokens:
+                err = int(cache["err"][0])
+                if err:
+                    raise RuntimeError(f"_greedy: a decode step ran past the RoPE table or the KV cache: error word {err}")
+                yield generated, tok in stop_ids, hiddens
+                return
+            yield generated, False, hiddens
+            emb = ops.splice_rows(m.llm.embed_tokens, None, torch.tensor([tok], dtype=torch.int64, device=dev), cfg.hidden_size)
+            h, _, _ = m.llm.forward(emb.view(1, 1, -1), None, kv_cache=cache)
+            hiddens.append(h)
+            last = h[0, -1:]
+
+    def _greedy(self, ids, images_clip, max_new_tokens, eos_token_id, mask_images=None, image_token_types=None, image_token_lengths=None,
+                region_masks=None, valid_region_masks_bool=None):
+        """HF `generate(do_sample=False, use_cache=True)` on one sample (MedPLIB.py:592-606; prepare_inputs_for_generation,
+        medplib_moe_llama.py:451-485): prefill of the spliced prompt, then single-token decode steps against the KV cache (_decode).
+        Returns (output_ids [1, L + n] on the host, [hidden states of the prompt, of each fed token])."""
+        generated, hiddens = [], []
+        for generated, _, hiddens in self._decode(ids, images_clip, max_new_tokens, (eos_token_id,), mask_images, image_token_types,
+                                                  image_token_lengths, region_masks, valid_region_masks_bool):
+            pass
+        return np.concatenate([ids, np.asarray(generated, dtype=np.int64)[None]], 1), list(hiddens)
 
     @torch.no_grad()
     def generate(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, **kwargs):
@@ -847,33 +915,70 @@ class MedPLIBForCausalLM(nn.Module):
         n = max(r.shape[0] for r in rows)
         return torch.from_numpy(np.stack([np.concatenate([r, np.full(n - r.shape[0], eos_token_id, np.int64)]) for r in rows]))
 
-    # ------------------------------------------------------------------ evaluate (MedPLIB.py:574-680)
     @torch.no_grad()
-    def evaluate(self, images_clip, images, input_ids, resize_list, original_size_list, region_masks=(), valid_region_masks_bool=(),
-                 max_new_tokens=512, tokenizer=None, attention_mask=None, inference_demo=False, mask_images=None,
-                 image_token_types=None, image_token_lengths=None, eos_token_id=2):
-        """Greedy generation with a KV cache (prefill + single-token decode steps), then one mask per sample from the hidden
-        state that predicts the first <SEG> (or position -2 when no <SEG> was generated) — MedPLIB.py:574-680.
-        Returns (output_ids [1, L + n_generated] int64 on the host, [pred_mask [1,H,W]]).
+    def generate_stream(self, input_ids, images_clip, images=None, temperature=1.0, top_p=1.0, max_new_tokens=256, stop_token_id=None,
+                        eos_token_id=2, stream_interval=1, sample_seed=0, resize_list=None, original_size_list=None, region_masks=(),
+                        valid_region_masks_bool=(), attention_mask=None, uniforms=None, debug=None, stop_check=None):
+        """The serving worker's token loop (model/serve/model_worker.py generate_stream) on one sample, as a generator: prefill, then one
+        decode step per token, yielding (new token ids so far, stopped, pred_mask) after tokens i with i % stream_interval == 0, after the
+        last one (i == max_new_tokens - 1) and at a stop (eos_token_id, stop_token_id, or stop_check(ids) -> True at a yield: the worker's
+        stop string).  Every yield's ids are a prefix of the next one's.
 
-        Reference quirk kept: the concatenated per-step hidden states cover the spliced prompt and the first n-1 generated
-        tokens (the last generated token is never fed back), i.e. one position FEWER than build_seg_token_mask(output_ids)
-        yields; the mask's final position is always False (shifted mask), so it is truncated to the hidden length."""
-        cfg, dev, m = self.config, self.device_, self.model
+        temperature < 1e-4: greedy, the tokens of generate().  Otherwise token i is drawn from softmax(logits / temperature) by inverse CDF
+        (ops.sample_rows) at the uniform the keyed generator gives for (sample_seed, i) (ops.sample_uniform): one seed, one answer; the
+        stream matches torch.multinomial in distribution, not draw by draw.  top_p is accepted and IGNORED: the reference's worker reads
+        it from the request and never uses it.
+        Decode path (last_decode_path): the captured graph when decode_with_graph and _graph_decode_ok() hold, max_new_tokens > 2 and no
+        `uniforms` is injected; the draw and the pick are then part of the captured step, and the host looks at the ids (and the cache's error
+        word) only at the yields.  Otherwise the token-by-token loop.  uniforms(i) -> float replaces the generator (tests); it runs on the
+        host, so it forces the loop.
+        pred_mask is None except in the stopping yield (an answer that runs into max_new_tokens gets none, as in the reference), and
+        there only when `images` (the SAM input, with resize_list and original_size_list as in evaluate()) was given and a generated id
+        is seg_token_idx: evaluate()'s mask of the first <SEG>.
+        debug: a list that receives (fp32 logits row on the host, u or None, token) for every kept token (tests; costs a sync per token)."""
         self.sync_side_streams()
-        self._require_merged("evaluate")
+        self._require_merged("generate_stream")
         ids = _np_ids(input_ids).astype(np.int64)
-        assert ids.shape[0] == 1, "evaluate() decodes one sample at a time, like the reference's validate_seg (vqa_infer.py:528)"
+        assert ids.shape[0] == 1, "generate_stream() decodes one sample, like the reference's worker"
+        if attention_mask is not None:
+            ids = ids[:, _np_ids(attention_mask)[0].astype(bool)]
+        max_new_tokens, every = int(max_new_tokens), max(1, int(stream_interval))
+        assert max_new_tokens >= 1
+        pick = _argmax_pick if temperature < 1e-4 else _SamplePick(temperature, sample_seed, self.device_, uniforms)
+        stop_ids = {int(t) for t in (eos_token_id, stop_token_id) if t is not None}
+        due = lambda i: i % every == 0 or i == max_new_tokens - 1            # noqa: E731  the reference's condition on the token number
+        looks = [i + 1 for i in range(max_new_tokens) if due(i)]
         was_training = self.training
         self.train(False)
+        steps = self._decode(ids, images_clip, max_new_tokens, stop_ids, region_masks=region_masks, valid_region_masks_bool=valid_region_masks_bool,
+                             pick=pick, looks=looks, host_pick=uniforms is not None, debug=debug)
+        try:
+            for generated, stopped, hiddens in steps:
+                i = len(generated) - 1
+                if not (stopped or due(i)):
+                    continue
+                new = list(generated)
+                if not stopped and stop_check is not None and stop_check(new):
+                    stopped = True
+                pred_mask = None
+                if stopped and images is not None and self.seg_token_idx in new:
+                    output_ids = np.concatenate([ids, np.asarray(new, dtype=np.int64)[None]], 1)
+                    pred_mask = self._seg_mask(output_ids, list(hiddens), images, resize_list, original_size_list)[0]
+                yield new, stopped, pred_mask
+                if stopped or i == max_new_tokens - 1:
+                    break
+        finally:
+            steps.close()
+            self.train(was_training)
+
+    def _seg_mask(self, output_ids, hiddens, images, resize_list, original_size_list, image_token_lengths=None):
+        """The mask of one decoded sample (MedPLIB.py:608-680): the hidden state that predicts the first <SEG> of output_ids (position -2
+        when there is none) -> text_hidden_fcs -> prompt + mask decoder over the SAM embedding of `images` -> [pred_mask [1, H, W]].
+        hiddens: the hidden states of the spliced prompt and of every fed token (the last generated token is never fed back)."""
+        cfg, dev, m = self.config, self.device_, self.model
         nfeat = cfg.image_token_len
-        output_ids, hiddens = self._greedy(ids, images_clip, max_new_tokens, eos_token_id, mask_images, image_token_types, image_token_lengths,
-                                           region_masks, valid_region_masks_bool)
         all_hidden = torch.cat(hiddens, 1)                                  # [1, S + n_gen - 1, d]
         n_hidden = all_hidden.shape[1]
-        if (output_ids[:, 1:] == self.seg_token_idx).sum() == 0 and inference_demo:
-            self.train(was_training)
-            return torch.from_numpy(output_ids), []
         n_ph = int((output_ids == IMAGE_TOKEN_INDEX).sum())
         has_region = bool((output_ids == REGION_TOKEN_INDEX).any())          # region ids expand 1:1, any base will do for the mask
         seg_plan = plan_splice(output_ids, None, None, nfeat if n_ph <= 1 else [nfeat] * n_ph, seg_token_idx=self.seg_token_idx,
@@ -893,6 +998,33 @@ class MedPLIBForCausalLM(nn.Module):
         osz = original_size_list[0]
         shape = tuple(osz.shape[-2:]) if hasattr(osz, "shape") else tuple(osz)
         _, pred_masks = self._postprocess(low_res, resize_list[:1], [shape])
+        return pred_masks
+
+    # ------------------------------------------------------------------ evaluate (MedPLIB.py:574-680)
+    @torch.no_grad()
+    def evaluate(self, images_clip, images, input_ids, resize_list, original_size_list, region_masks=(), valid_region_masks_bool=(),
+                 max_new_tokens=512, tokenizer=None, attention_mask=None, inference_demo=False, mask_images=None,
+                 image_token_types=None, image_token_lengths=None, eos_token_id=2):
+        """Greedy generation with a KV cache (prefill + single-token decode steps), then one mask per sample from the hidden
+        state that predicts the first <SEG> (or position -2 when no <SEG> was generated) — MedPLIB.py:574-680.
+        Returns (output_ids [1, L + n_generated] int64 on the host, [pred_mask [1,H,W]]).
+
+        Reference quirk kept: the concatenated per-step hidden states cover the spliced prompt and the first n-1 generated
+        tokens (the last generated token is never fed back), i.e. one position FEWER than build_seg_token_mask(output_ids)
+        yields; the mask's final position is always False (shifted mask), so it is truncated to the hidden length."""
+        cfg, dev, m = self.config, self.device_, self.model
+        self.sync_side_streams()
+        self._require_merged("evaluate")
+        ids = _np_ids(input_ids).astype(np.int64)
+        assert ids.shape[0] == 1, "evaluate() decodes one sample at a time, like the reference's validate_seg (vqa_infer.py:528)"
+        was_training = self.training
+        self.train(False)
+        output_ids, hiddens = self._greedy(ids, images_clip, max_new_tokens, eos_token_id, mask_images, image_token_types, image_token_lengths,
+                                           region_masks, valid_region_masks_bool)
+        if (output_ids[:, 1:] == self.seg_token_idx).sum() == 0 and inference_demo:
+            self.train(was_training)
+            return torch.from_numpy(output_ids), []
+        pred_masks = self._seg_mask(output_ids, hiddens, images, resize_list, original_size_list, image_token_lengths)
         self.train(was_training)
         return torch.from_numpy(output_ids), pred_masks
 

@@ -855,6 +855,28 @@ def argmax_rows(x):
     return out
 
 
+def sample_rows(logits, u, temperature):
+    """Temperature sampling of one column per row (mp_sample_rows_f32): the smallest i whose cumulative softmax(logits / temperature) weight
+    exceeds u.  logits fp32 [rows, cols]; u fp32 [rows] in [0, 1] (sample_uniform / sample_uniform_dev); int64 [rows] on the device."""
+    _chk(logits, torch.float32, "sample_rows.logits"); _chk(u, torch.float32, "sample_rows.u")
+    assert logits.dim() == 2 and logits.stride(1) == 1 and u.dim() == 1 and u.is_contiguous() and u.numel() == logits.shape[0]
+    out = torch.empty(logits.shape[0], dtype=torch.int64, device=logits.device)
+    lib().call("mp_sample_rows_f32", _p(logits), logits.stride(0), logits.shape[0], logits.shape[1], 1.0 / float(temperature), _p(u), _p(out),
+               _stream())
+    return out
+
+
+def sample_uniform(seed, step, device):
+    """The uniform that picks generated token `step` of a request: the keyed generator of the gate draws under key (seed, step); fp32 [1]
+    in [2^-25, 1] (1.0 itself with probability 2^-24: include/medplib_hip.h)."""
+    return gate_noise(1, seed, step, False, device)
+
+
+def sample_uniform_dev(seed, step_dev, device):
+    """sample_uniform with the step read on the device (int32 [1]): what a captured decode step draws at every replay."""
+    return gate_noise_dev(1, seed, step_dev, 1, False, device)
+
+
 def swiglu_interleave(gate, up):
     """Pack gate/up projection weights [ff, d] into the row order the SWIGLU_PAIR epilogue expects: blocks of 32 gate rows
     followed by the 32 matching up rows.  (Pure data movement.)"""
