@@ -6,6 +6,7 @@
 // (window_partition/unpartition), :381-421 (add_decomposed_rel_pos), :18-56 (Adapter_Layer), :424-455 (PatchEmbed),
 // HF CLIPVisionEmbeddings.
 #include "common.h"
+#include "gemm_common.h"
 
 namespace {
 
@@ -283,6 +284,8 @@ __global__ void adaptive_avgpool_tokens_kernel(const bf16_t* __restrict__ x, bf1
 
 // ---- first layer of MaskTokenEncoder: Conv2d(1, CO, k3, s2, p1) + GELU on a single-channel mask image, NHWC bf16 output
 //      (medplib_arch.py:84-85).  One thread per (pixel, 8 output channels): 9 taps x 8 FMAs, HBM-bound on the output.
+//      Rounding points of the bf16 module: the convolution's output is rounded to bf16, the GELU reads that value -- so this kernel equals
+//      mp_gelu_fwd_bf16(mp_conv3x3s2_c1_pre_bf16(.)) of the training forward to the bit (same taps in the same order, same GELU function).
 template <typename TIN>
 __global__ void conv3x3s2_c1_gelu_kernel(const TIN* __restrict__ img, const float* __restrict__ w, const float* __restrict__ bias,
                                          bf16_t* __restrict__ out, int n, int H, int W, int OH, int OW, int CO) {
@@ -308,7 +311,7 @@ __global__ void conv3x3s2_c1_gelu_kernel(const TIN* __restrict__ img, const floa
     }
   bf16x8 o;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = (bf16_t)gelu_erf(acc[j]);
+  for (int j = 0; j < 8; ++j) o[j] = (bf16_t)gelu_erf_fast((float)(bf16_t)acc[j]);
   *reinterpret_cast<bf16x8*>(out + pix * CO + co) = o;
 }
 
