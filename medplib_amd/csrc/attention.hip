@@ -50,6 +50,7 @@ __device__ __forceinline__ int k_off(int r, int c) {  // byte offset of 16-B chu
 
 template <int D, bool VT_SCALAR>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
+  const int sk_rows = a.Sk;         // row length of key_valid: the tensor's key count, not the device-side one
   if (a.sk_dev) a.Sk = min(a.Sk, a.sk_dev[0]);
   constexpr int KT = 64;            // keys per tile
   constexpr int CH = D / 8;         // 16-B chunks per row
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   const bf16_t* Qb = a.Q + b * a.q_sb + (int64_t)h * D;
   const bf16_t* Kb = a.K + b * a.k_sb + (int64_t)h * D;
   const bf16_t* Vb = a.V + b * a.v_sb + (int64_t)h * D;
-  const uint8_t* kv = a.key_valid ? a.key_valid + (int64_t)b * a.Sk : nullptr;
+  const uint8_t* kv = a.key_valid ? a.key_valid + (int64_t)b * sk_rows : nullptr;
 
   // Q fragments (A operand): row = qw0 + fr, k = kk*32 + fq*8 .. +8
   bf16x8 qf[KS];
@@ -322,6 +323,7 @@ __device__ __forceinline__ float max_over_rows(float v) {
 
 template <int D, bool GENERAL, int KT, bool TUNED = true>
 __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(AttnArgs a) {
+  const int sk_rows = a.Sk;         // row length of key_valid: the tensor's key count, not the device-side one
   if (a.sk_dev) a.Sk = min(a.Sk, a.sk_dev[0]);
   constexpr int CH = D / 8, NF = D / 16, KS = D / 32;
   constexpr int NST = 128 / KT;                   // stages of the K / V ring (2 x 64 keys or 4 x 32 keys: the same bytes)
@@ -359,7 +361,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(AttnArgs a) {
   const bf16_t* Qb = a.Q + b * a.q_sb + (int64_t)h * D;
   const bf16_t* Kb = a.K + b * a.k_sb + (int64_t)h * D;
   const bf16_t* Vb = a.V + b * a.v_sb + (int64_t)h * D;
-  const uint8_t* kv = (GENERAL && a.key_valid) ? a.key_valid + (int64_t)b * a.Sk : nullptr;
+  const uint8_t* kv = (GENERAL && a.key_valid) ? a.key_valid + (int64_t)b * sk_rows : nullptr;
   const float* relh = (GENERAL && a.rel_h) ? a.rel_h + (int64_t)bh * a.Sq * a.kh : nullptr;
   const float* relw = (GENERAL && a.rel_w) ? a.rel_w + (int64_t)bh * a.Sq * a.kw : nullptr;
 

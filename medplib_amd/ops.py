@@ -355,7 +355,12 @@ def gemm_batched_res(a, w, residual, out, m_dev=None):
 
 
 def attention(q, k, v, out=None, causal=False, key_valid=None, rel_h=None, rel_w=None, scale=None, variant=0, sk_dev=None):
-    """q,k,v: [B,S,H,D] bf16 views (stride(3)==1, stride(2)==D); returns [B,Sq,H*D] bf16."""
+    """q,k,v: [B,S,H,D] bf16 views (stride(3)==1, stride(2)==D); returns [B,Sq,H*D] bf16.
+    The causal mask is top-left aligned (key kj <= query qi); key_valid [B,Sk] uint8 is read per key (holes allowed) and keeps the
+    tensor's row length Sk when sk_dev shortens the keys.  A query row with NO admissible key (every key masked) gets an output of
+    exactly 0 (attention_fwd_lse: lse2 = +inf; attention_bwd: zero dQ, nothing added to dK / dV) -- unlike HF eager, which averages V
+    uniformly over such a row.  The model never produces one: collate pads on the right and the splice extends on the left with valid
+    rows, so key 0 is always valid (tests/test_gpu_attention_edges.py pins this behaviour)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _chk(t, torch.bfloat16, "attention." + n)
         assert t.dim() == 4 and t.stride(3) == 1 and t.stride(2) == t.shape[3]
