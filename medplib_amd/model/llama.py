@@ -64,8 +64,16 @@ class LlamaStack:
         self.training = True
         self.rts_uniform_provider = None   # callable(layer_idx, T, E) -> fp32 [T,E] gate draws (RTS uniforms / top-2 Gumbel) or None
         self.gate_pass = 0                 # forward passes so far: part of the key of the stateless gate-draw generator
-        self._pass_dev = None              # int32 [1] on the device: the pass number of the decode step being captured (decode_step)
         self.ep = None                     # ExpertParallel (expert_parallel.py) once enable_expert_parallel() sharded the experts
+        self.lora = None                   # LoRAState: written by llama_lora.enable_lora / medplib.merge_and_unload, read by llama_lora and medplib
+        # per-pass state (names and lifetimes are an interface: medplib.model_forward, bench.py, oracle/parity.py and the tests use them)
+        self.needed_rows = None            # (rows int64, mask uint8) of the rows something reads: model_forward / a test sets and clears it around a pass; forward, forward_train read
+        self.pruned_rows = None            # rows the last layer's MLP ran on: model_forward clears and reads it, _mlp_gather_scatter / forward_train write it
+        self.layer_events = None           # a torch.cuda.Event per layer: model_forward creates them (gate_towers) for the towers, _mlp_gather_scatter records
+        self.folded_layers = 0             # layers the last forward ran with folded norms: forward writes, bench.py / oracle/parity.py / tests read
+        self.last_gate_inputs = None       # per MoE layer, the stream before the post-attention norm: forward(collect_routing=True) writes, oracle/parity.py reads
+        self._draws_key = None             # what _draws_all was drawn for: _gate_draws writes and reads; medplib._decode_graph and tests reset it to None
+        self._draws_all = None             # fp32 [L * T * E] gate draws of one pass, all layers: _gate_draws writes and slices
         self.fuse_moe_gather_scatter = True   # top-1, one rank: dispatch / combine folded into the expert GEMMs
         self.fuse_decode_routing = True       # decode rows: post-attention norm + gate + routing in one launch
         # RoPE in the qkv GEMM's epilogue (mp_gemm_qkv_rope_bf16) wants the q / k head rows interleaved in blocks of 32; the plain
@@ -105,7 +113,7 @@ class LlamaStack:
                     lw[k] = lw[k][ids[0]:ids[-1] + 1].contiguous()
             for k in ("gu", "down"):                             # the expert-parallel training path keeps the unfused adapter kernels
                 lw.pop(k + "_x", None)
-                if getattr(self, "lora", None) is not None:
+                if self.lora is not None:
                     self.lora.ext.pop((i, k), None)
         self.ep = ep
 
@@ -178,9 +186,9 @@ class LlamaStack:
         cf = cfg.capacity_factor if self.training else cfg.eval_capacity_factor
         return max(int(math.ceil(T / cfg.num_experts * cf * cfg.top_k_experts)), cfg.min_capacity)
 
-    def _gate_draws(self, i, T, E, gumbel):
+    def _gate_draws(self, i, T, E, gumbel, pass_dev=None):
         """Random draws of the gate: an injected provider (tests: the same numbers go to the oracle) or, when the config asks for
-        DeepSpeed's sampling behaviour, the stateless generator keyed by (seed, forward pass, layer)."""
+        DeepSpeed's sampling behaviour, the stateless generator keyed by (seed, forward pass, layer).  pass_dev: decode_step's."""
         if self.rts_uniform_provider is not None:
             return self.rts_uniform_provider(i, T, E)
         if not self.cfg.moe_gate_sampling:
@@ -188,9 +196,8 @@ class LlamaStack:
         # the generator is keyed by (seed, offset + index) and a pass's layers occupy consecutive offsets: ONE launch per forward pass draws
         # for all layers (the same numbers as a launch per layer, which sat between every layer's routing kernel and its expert GEMMs)
         L = len(self.layers)
-        pass_dev = self._pass_dev
         key = (self.gate_pass, T, E, bool(gumbel), pass_dev is not None)
-        if getattr(self, "_draws_key", None) != key:
+        if self._draws_key != key:
             if pass_dev is not None:       # a decode step under a HIP graph: the pass number is read on the device (decode_step)
                 self._draws_all = ops.gate_noise_dev(L * T * E, self.cfg.moe_gate_seed, pass_dev, L * T * E, gumbel, self.device)
             else:
@@ -198,69 +205,80 @@ class LlamaStack:
             self._draws_key = key
         return self._draws_all[i * T * E:(i + 1) * T * E]
 
-    def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None):
+    def _expert_gemv_rows(self, T):
+        """Whether T rows of a MoE layer take the per-row expert GEMVs (the decode rows): one rank, at most 8 rows, no residual MoE."""
+        return self.ep is None and T <= 8 and not self.cfg.use_residual
+
+    def _expert_gemvs_top1(self, lw, h, x, expert, slot, weight):
+        """Decode rows, top-1: each row streams its own expert's matrices (GEMV with a device-side expert index); the combine weight, the
+        capacity drop and the residual ride in the down projection's epilogue.  Behind _mlp's routing and behind decode_step's fused one."""
+        act = ops.gemv(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR, w_index=expert)
+        return ops.gemv(act, lw["down"], residual=x, w_index=expert, row_scale=weight, row_keep=slot)
+
+    def _expert_gemvs_top2(self, lw, h, x, expert, slot, weight):
+        """Decode rows, top-2: the 2T (token, choice) entries stream their experts' matrices; the down projection adds both weighted expert
+        outputs and the residual in moe_combine's order.  Behind _mlp's routing and behind decode_step's fused one."""
+        act = ops.gemv_top2_gate_up(h, lw["gu"], expert, slot)
+        return ops.gemv_top2_down(act, lw["down"], expert, slot, weight, x)
+
+    def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None, pass_dev=None):
         """x + MLP(h): h = post-attention RMSNorm output [T,d], x = residual stream [T,d]; gate = (logits, gates) when the caller's fused
-        norm kernel already produced them (ops.rmsnorm_gate)."""
-        cfg = self.cfg
-        T = x.shape[0]
+        norm kernel already produced them (ops.rmsnorm_gate); needed = (rows, mask) when only those output rows are read (the last layer);
+        rstd: the folded post-attention norm (h is None then).  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
+        cfg, T = self.cfg, x.shape[0]
         if i not in self.moe_layers:
             if T <= 8:
                 return ops.gemv(ops.gemv(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR), lw["down"], residual=x), None, None
             act = ops.gemm(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR)       # silu(gate)*up fused into the GEMM epilogue
             return ops.gemm(act, lw["down"], residual=x), None, None
-        E, ff, d = cfg.num_experts, cfg.intermediate_size, cfg.hidden_size
-        cap = self.capacity(T)
-        k = cfg.top_k_experts
+        E, k, cap = cfg.num_experts, cfg.top_k_experts, self.capacity(T)
         logits, gates = gate if gate is not None else ops.moe_gate(h, lw["wg"])
-        if k == 1 and self.ep is None and T <= 8 and not cfg.use_residual:
-            # decode rows: each row streams its own expert's matrices (GEMV with a device-side expert index); the combine weight,
-            # the capacity drop and the residual ride in the down projection's epilogue
-            # (no gate draws: random token selection only acts when an expert is over capacity, and capacity >= T for these rows
-            #  only when cap >= T; otherwise the draws are generated as usual)
-            draws = None if cap >= T else self._gate_draws(i, T, E, gumbel=False)
+        if k == 1 and self._expert_gemv_rows(T):
+            # (no gate draws: random token selection only acts when an expert is over capacity; below cap >= T the draws are generated as usual)
+            draws = None if cap >= T else self._gate_draws(i, T, E, False, pass_dev)
             expert, slot, weight, kept, counts, l_aux = ops.moe_route_top1(gates, cap, draws)
-            act = ops.gemv(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR, w_index=expert)
-            out = ops.gemv(act, lw["down"], residual=x, w_index=expert, row_scale=weight, row_keep=slot)
-            return out, l_aux, (expert, slot, counts)
-        if k == 2 and self.ep is None and T <= 8 and not cfg.use_residual:
-            # decode rows, top-2: the 2T (token, choice) entries stream their experts' matrices (GEMVs with a device-side expert index);
-            # the down projection adds both weighted expert outputs and the residual in moe_combine's order (decode_step's fused form
-            # takes the same two launches behind its one-launch routing)
-            expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2(gates, logits, cap, self._gate_draws(i, T, E, gumbel=True))
-            act = ops.gemv_top2_gate_up(h, lw["gu"], expert, slot)
-            return ops.gemv_top2_down(act, lw["down"], expert, slot, weight, x), l_aux, (expert, slot, counts)
+            return self._expert_gemvs_top1(lw, h, x, expert, slot, weight), l_aux, (expert, slot, counts)
+        if k == 2 and self._expert_gemv_rows(T):
+            expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2(gates, logits, cap, self._gate_draws(i, T, E, True, pass_dev))
+            return self._expert_gemvs_top2(lw, h, x, expert, slot, weight), l_aux, (expert, slot, counts)
         if k == 1 and self.ep is None and self.fuse_moe_gather_scatter and not cfg.use_residual:
-            # top-1 on one rank: the dispatch is a row gather in the gate|up GEMM's operand fetch and the combine (gate weight and
-            # the layer's residual add) a row scatter in the down GEMM's epilogue; every routed token's row is written exactly once,
-            # the capacity-dropped ones get the residual stream from a fill kernel
-            expert, slot, weight, kept, counts, l_aux, slot_token = ops.moe_route_top1(
-                gates, cap, self._gate_draws(i, T, E, gumbel=False), want_slot_token=True)
-            act = torch.empty((E, cap, ff), dtype=torch.bfloat16, device=x.device)
-            if needed is not None:
-                self.pruned_rows = int(getattr(self, "needed_rows")[0].numel())      # the pruning HAPPENED (model_forward reports only this)
-                # the last layer: only the rows something reads go through the experts (the routing above saw every token: capacity drops,
-                # l_aux and the counts are those of the whole batch); a row that is not computed keeps the residual stream, which nobody reads
-                slot_token, kept = ops.moe_filter_slots(slot_token, kept, needed)
-            if ops.GEMM_TIMER is not None:
-                ops.GEMM_TIMER.batched_tag = i          # the expert GEMMs are credited with the rows `kept` holds after the region
-            ev = getattr(self, "layer_events", None)
-            if ev is not None and i < len(ev):
-                ev[i].record()          # "layer i's expert GEMMs start here": what the frozen towers of the NEXT step gate their layers on (medplib.model_forward)
-            if rstd is not None:        # folded post-attention norm: the experts read the raw stream, W carries ln2, the epilogue applies rstd
-                ops.gemm_batched_rows(x, lw["gu_f"], act, kept, a_rows=slot_token, act=ops.ACT_SWIGLU_PAIR, rows_stride=cap, a_row_scale=rstd)
-            else:
-                ops.gemm_batched_rows(h, lw["gu"], act, kept, a_rows=slot_token, act=ops.ACT_SWIGLU_PAIR, rows_stride=cap)
-            # Round 4: the combine writes INTO the residual stream (out = residual = x).  Every (routed row, 16-byte column piece) has
-            # exactly one owner in the down projection's epilogue — a tile, or one unit's share of a split tail tile — which reads the
-            # residual piece and stores the sum at the same address; a capacity-dropped token's row is simply left as it is, which is
-            # DeepSpeed's result for it (x + 0).  The moe_fill_dropped launch per layer and the [T, d] output buffer are gone (same bits:
-            # test_moe_fused_gather_scatter_matches_unfused).  No gradient flows here (the LoRA path keeps its own forward).
-            ops.gemm_batched_rows(act, lw["down"], x, kept, c_rows=slot_token, c_scale=weight, residual=x, rows_stride=cap)
-            return x, l_aux, (expert, slot, counts)
-        if k == 1:
-            expert, slot, weight, kept, counts, l_aux = ops.moe_route_top1(gates, cap, self._gate_draws(i, T, E, gumbel=False))
+            return self._mlp_gather_scatter(i, lw, h, x, gates, cap, needed, rstd, pass_dev)
+        return self._mlp_dispatch_combine(i, lw, h, x, logits, gates, cap, pass_dev)
+
+    def _mlp_gather_scatter(self, i, lw, h, x, gates, cap, needed, rstd, pass_dev):
+        """Top-1 on one rank: the dispatch is a row gather in the gate|up GEMM's operand fetch and the combine (gate weight and the layer's
+        residual add) a row scatter in the down GEMM's epilogue; every routed token's row is written exactly once."""
+        E, ff, T = self.cfg.num_experts, self.cfg.intermediate_size, x.shape[0]
+        expert, slot, weight, kept, counts, l_aux, slot_token = ops.moe_route_top1(gates, cap, self._gate_draws(i, T, E, False, pass_dev), want_slot_token=True)
+        act = torch.empty((E, cap, ff), dtype=torch.bfloat16, device=x.device)
+        if needed is not None:
+            self.pruned_rows = int(needed[0].numel())      # the pruning HAPPENED (model_forward reports only this)
+            # the last layer: only the rows something reads go through the experts (the routing above saw every token: capacity drops,
+            # l_aux and the counts are those of the whole batch); a row that is not computed keeps the residual stream, which nobody reads
+            slot_token, kept = ops.moe_filter_slots(slot_token, kept, needed[1])
+        if ops.GEMM_TIMER is not None:
+            ops.GEMM_TIMER.batched_tag = i          # the expert GEMMs are credited with the rows `kept` holds after the region
+        if self.layer_events is not None and i < len(self.layer_events):
+            self.layer_events[i].record()   # "layer i's expert GEMMs start here": what the frozen towers of the NEXT step gate their layers on (medplib.model_forward)
+        if rstd is not None:        # folded post-attention norm: the experts read the raw stream, W carries ln2, the epilogue applies rstd
+            ops.gemm_batched_rows(x, lw["gu_f"], act, kept, a_rows=slot_token, act=ops.ACT_SWIGLU_PAIR, rows_stride=cap, a_row_scale=rstd)
         else:
-            expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2(gates, logits, cap, self._gate_draws(i, T, E, gumbel=True))
+            ops.gemm_batched_rows(h, lw["gu"], act, kept, a_rows=slot_token, act=ops.ACT_SWIGLU_PAIR, rows_stride=cap)
+        # The combine writes INTO the residual stream (out = residual = x).  Every (routed row, 16-byte column piece) has exactly one owner in
+        # the down projection's epilogue — a tile, or one unit's share of a split tail tile — which reads the residual piece and stores the sum
+        # at the same address; a capacity-dropped token's row is left as it is, which is DeepSpeed's result for it (x + 0) (same bits as the
+        # unfused form: test_moe_fused_gather_scatter_matches_unfused).  No gradient flows here (the LoRA path keeps its own forward).
+        ops.gemm_batched_rows(act, lw["down"], x, kept, c_rows=slot_token, c_scale=weight, residual=x, rows_stride=cap)
+        return x, l_aux, (expert, slot, counts)
+
+    def _mlp_dispatch_combine(self, i, lw, h, x, logits, gates, cap, pass_dev):
+        """The generic MoE branch (top-2, unfused top-1, expert parallelism, residual MoE): dispatch into capacity slabs, batched expert GEMM pair, combine."""
+        cfg = self.cfg
+        E, ff, d, k, T = cfg.num_experts, cfg.intermediate_size, cfg.hidden_size, cfg.top_k_experts, x.shape[0]
+        if k == 1:
+            expert, slot, weight, kept, counts, l_aux = ops.moe_route_top1(gates, cap, self._gate_draws(i, T, E, False, pass_dev))
+        else:
+            expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2(gates, logits, cap, self._gate_draws(i, T, E, True, pass_dev))
         if self.ep is not None:
             # slabs of capx + 1 rows: capx = the capacity agreed over the expert-parallel group for this pass (ranks see different
             # T), the extra row is the header that carries the row count through the same all-to-all (expert_parallel.py)
@@ -278,13 +296,14 @@ class LlamaStack:
         y = torch.empty((E, cap, d), dtype=torch.bfloat16, device=h.device)
         ops.gemm_batched(act, lw["down"], y, m_dev=kept)
         if cfg.use_residual:
-            # residual MoE: the routed output and a dense MLP of the same input, mixed by a learned two-way softmax
-            moe = ops.moe_combine(y, expert, slot, weight, None, cap, top_k=k)
-            mlp = ops.gemm(ops.gemm(h, lw["res_gu"], act=ops.ACT_SWIGLU_PAIR), lw["res_down"])
-            coef = ops.gemm(h, lw["coef_w"], bias=lw["coef_b"])
-            return ops.moe_residual_mix(x, moe, mlp, coef), l_aux, (expert, slot, counts)
-        out = ops.moe_combine(y, expert, slot, weight, x, cap, top_k=k)
-        return out, l_aux, (expert, slot, counts)
+            return self._residual_mix(lw, h, x, ops.moe_combine(y, expert, slot, weight, None, cap, top_k=k)), l_aux, (expert, slot, counts)
+        return ops.moe_combine(y, expert, slot, weight, x, cap, top_k=k), l_aux, (expert, slot, counts)
+
+    def _residual_mix(self, lw, h, x, moe):
+        """Residual MoE: the routed output and a dense MLP of the same input, mixed by a learned two-way softmax."""
+        mlp = ops.gemm(ops.gemm(h, lw["res_gu"], act=ops.ACT_SWIGLU_PAIR), lw["res_down"])
+        coef = ops.gemm(h, lw["coef_w"], bias=lw["coef_b"])
+        return ops.moe_residual_mix(x, moe, mlp, coef)
 
     def _experts_parallel(self, lw, buf, kept, cap):
         """MOELayer with ep_size > 1: all-to-all the routed rows to the ranks that own the experts, run each local expert over the
@@ -329,6 +348,36 @@ class LlamaStack:
                 "v": [torch.empty(shape, dtype=torch.bfloat16, device=self.device) for _ in self.layers],
                 "err": torch.zeros(1, dtype=torch.int32, device=self.device)}
 
+    def _lin(self, a, w, **kw):
+        """A projection of a [T, K]: a handful of rows (the single-token decode steps) are a weight stream -> GEMV kernel (HBM-bound), else GEMM."""
+        return ops.gemv(a, w, **kw) if a.shape[0] <= 8 else ops.gemm(a, w, **kw)
+
+    def _qkv(self, lw, x, S, pos0, folded):
+        """input_layernorm + fused qkv projection + RoPE of the rows x [B*S, d] at positions pos0 .. pos0 + S - 1 -> qkv [B*S, 3d]."""
+        cfg = self.cfg
+        H, D, (T, d) = cfg.num_attention_heads, cfg.head_dim, x.shape
+        if folded:                         # x -> rstd1; qkv = (x W'^T) * rstd1 -> RoPE
+            rstd1, _, _ = ops.rmsnorm_gate_rstd(x, lw["ln1"], cfg.rms_norm_eps)
+            return ops.gemm_qkv_rope(x, lw["qkv_rope_f"], self.cos, self.sin, S, H, D, pos_offset=pos0, out=ops.padded_rows(T, 3 * d, x.device), row_scale=rstd1)
+        h = ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps)
+        if self.fuse_rope and T > 8:       # RoPE in the epilogue (row stride of the qkv buffer kept off multiples of 8 KiB: ops.padded_rows)
+            return ops.gemm_qkv_rope(h, lw["qkv_rope"], self.cos, self.sin, S, H, D, pos_offset=pos0, out=ops.padded_rows(T, 3 * d, x.device))
+        qkv = self._lin(h, lw["qkv"])
+        ops.rope_qk_(qkv, self.cos, self.sin, S, H, D, pos_offset=pos0)
+        return qkv
+
+    def _post_attention_norm(self, i, lw, x, folded):
+        """post_attention_layernorm of the stream x -> (h, gate, rstd) as _mlp takes them.  Folded: rstd2 and the gate (from HF's bf16 h), no h (the
+        experts read x with W''); MoE layer of an rmsnorm_gate dimension: norm and gate in one pass over the rows (the two kernels' bits); else the norm."""
+        cfg = self.cfg
+        if folded:
+            rstd2, lg, gt = ops.rmsnorm_gate_rstd(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"])
+            return None, (lg, gt), rstd2
+        if i in self.moe_layers and x.shape[1] in ops.RMSNORM_GATE_DIMS and x.shape[0] > 8:
+            h, lg, gt = ops.rmsnorm_gate(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"])
+            return h, (lg, gt), None
+        return ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps), None, None
+
     def forward(self, inputs_embeds, key_valid=None, collect_routing=False, kv_cache=None):
         """inputs_embeds [B,S,d] bf16; key_valid uint8 [B,S] (1 = real token) or None.
         With kv_cache: the S new tokens sit at positions cache.len .. cache.len+S-1, their K/V are appended and attention runs
@@ -339,47 +388,21 @@ class LlamaStack:
         H, D = cfg.num_attention_heads, cfg.head_dim
         x = inputs_embeds.reshape(B * S, d)
         aux, routing, gate_inputs = [], [], []
-        nr = getattr(self, "needed_rows", None)             # (rows, mask) from model_forward: the output rows something reads, or None
-        needed_mask = nr[1] if (nr is not None and not collect_routing and kv_cache is None and nr[1].numel() == B * S) else None
+        nr = self.needed_rows               # (rows, mask) from model_forward: the output rows something reads, or None
+        needed = nr if (nr is not None and not collect_routing and kv_cache is None and nr[1].numel() == B * S) else None
         self.gate_pass += 1
         pos0 = kv_cache["len"] if kv_cache is not None else 0
         if kv_cache is not None and pos0 + S > kv_cache["k"][0].shape[1]:
             raise ValueError(f"LlamaStack.forward: positions {pos0}..{pos0 + S - 1} do not fit the KV cache of {kv_cache['k'][0].shape[1]} rows")
         self.ensure_positions(pos0 + S)
-        # a handful of rows (the single-token decode steps): the projections are weight streams -> GEMV kernel (HBM-bound)
-        lin = (lambda a, w, **kw: ops.gemv(a, w, **kw)) if B * S <= 8 else (lambda a, w, **kw: ops.gemm(a, w, **kw))
-        ff = cfg.intermediate_size
-        # folded norms (config.fold_input_norm): frozen top-1 MoE layers of 320-row-kernel shapes, one rank, no intermediate capture
+        # folded norms (config.fold_input_norm): frozen top-1 MoE layers of 320-row-kernel shapes, one rank, no KV cache
         fold = ("qkv_rope_f" in self.layers[0] if self.layers else False) and kv_cache is None and self.ep is None and self.fuse_moe_gather_scatter \
-            and d in ops.RMSNORM_GATE_DIMS and ops.gemm_fold_ok(B * S, 3 * d, d) and ops.gemm_fold_ok(self.capacity(B * S), 2 * ff, d)
+            and d in ops.RMSNORM_GATE_DIMS and ops.gemm_fold_ok(B * S, 3 * d, d) and ops.gemm_fold_ok(self.capacity(B * S), 2 * cfg.intermediate_size, d)
         self.folded_layers = 0
+        last = len(self.layers) - 1
         for i, lw in enumerate(self.layers):
-            if fold and "qkv_rope_f" in lw:
-                # x -> rstd1; qkv = (x W'^T) * rstd1 -> RoPE; attention; o_proj + residual; x -> rstd2 + gate (from HF's bf16 h); experts on x with W''
-                rstd1, _, _ = ops.rmsnorm_gate_rstd(x, lw["ln1"], cfg.rms_norm_eps)
-                qkv = ops.gemm_qkv_rope(x, lw["qkv_rope_f"], self.cos, self.sin, S, H, D, pos_offset=pos0, out=ops.padded_rows(B * S, 3 * d, x.device),
-                                        row_scale=rstd1)
-                q5 = qkv.unflatten(0, (B, S)).unflatten(2, (3, H, D))
-                attn = ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], causal=True, key_valid=key_valid)
-                x = lin(attn.view(B * S, d), lw["o"], residual=x)
-                x_gate_in = x.clone() if collect_routing else None          # (tests / parity only, as below)
-                rstd2, lg, gt = ops.rmsnorm_gate_rstd(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"])
-                x, l_aux, r = self._mlp(i, lw, None, x, gate=(lg, gt), needed=needed_mask if i == len(self.layers) - 1 else None, rstd=rstd2)
-                aux.append(l_aux)
-                if collect_routing:
-                    routing.append(r)
-                    gate_inputs.append(x_gate_in)
-                self.folded_layers += 1
-                continue
-            h = ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps)
-            if self.fuse_rope and B * S > 8:
-                # (row stride of the qkv buffer kept off multiples of 8 KiB: ops.padded_rows)
-                qkv = ops.gemm_qkv_rope(h, lw["qkv_rope"], self.cos, self.sin, S, H, D, pos_offset=pos0,
-                                        out=ops.padded_rows(B * S, 3 * d, x.device))                       # RoPE in the epilogue
-            else:
-                qkv = lin(h, lw["qkv"])
-                ops.rope_qk_(qkv, self.cos, self.sin, S, H, D, pos_offset=pos0)
-            q5 = qkv.unflatten(0, (B, S)).unflatten(2, (3, H, D))
+            folded = fold and "qkv_rope_f" in lw
+            q5 = self._qkv(lw, x, S, pos0, folded).unflatten(0, (B, S)).unflatten(2, (3, H, D))
             if kv_cache is not None:
                 kv_cache["k"][i][:, pos0:pos0 + S].copy_(q5[:, :, 1])
                 kv_cache["v"][i][:, pos0:pos0 + S].copy_(q5[:, :, 2])
@@ -388,24 +411,19 @@ class LlamaStack:
                 attn = ops.attention(q5[:, :, 0], kv_cache["k"][i][:, :pos0 + 1], kv_cache["v"][i][:, :pos0 + 1], causal=False)
             else:
                 attn = ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], causal=True, key_valid=key_valid)
-            x = lin(attn.view(B * S, d), lw["o"], residual=x)
+            x = self._lin(attn.view(B * S, d), lw["o"], residual=x)
             # (tests / parity only: the layer's own gate input, copied before the combine writes the MLP output into the residual stream — the
             #  layer-local routing check of oracle/parity.py recomputes the gate from it)
             x_gate_in = x.clone() if (collect_routing and i in self.moe_layers) else None
-            if i in self.moe_layers and d in ops.RMSNORM_GATE_DIMS and B * S > 8:
-                # post-attention norm and the MoE gate in one pass over the rows (bit-identical with the two kernels)
-                h, lg, gt = ops.rmsnorm_gate(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"])
-                x, l_aux, r = self._mlp(i, lw, h, x, gate=(lg, gt), needed=needed_mask if i == len(self.layers) - 1 else None)
-            else:
-                h = ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps)
-                # (the row set also reaches the MoE branch behind the unfused norm — hidden sizes without an rmsnorm_gate instantiation, the tiny
-                #  test dims: _mlp prunes in its top-1 gather / scatter branch whichever kernel produced the gate)
-                x, l_aux, r = self._mlp(i, lw, h, x, needed=needed_mask if (i in self.moe_layers and i == len(self.layers) - 1) else None)
+            h, gate, rstd = self._post_attention_norm(i, lw, x, folded)
+            # (the last layer's row set goes to _mlp whatever produced the gate: only the top-1 gather / scatter branch prunes, a dense layer ignores it)
+            x, l_aux, r = self._mlp(i, lw, h, x, gate=gate, needed=needed if i == last else None, rstd=rstd)
             if l_aux is not None:
                 aux.append(l_aux)
                 if collect_routing:
                     routing.append(r)
                     gate_inputs.append(x_gate_in)
+            self.folded_layers += int(folded)
         if kv_cache is not None:
             kv_cache["len"] = pos0 + S
         out = ops.rmsnorm(x, self.norm_w, cfg.rms_norm_eps)
@@ -425,16 +443,9 @@ class LlamaStack:
         pass_dev (int32 [1] on the device, or None): the number of this forward pass, read on the device by the gate's random draws
         (moe_gate_sampling) instead of the host counter `gate_pass` — a captured step then draws, at every replay, what the token-by-token
         loop draws for that pass; the caller advances it with the counters."""
-        self._pass_dev = pass_dev
-        try:
-            return self._decode_step(emb, kv_cache, counters)
-        finally:
-            self._pass_dev = None
-
-    def _decode_step(self, emb, kv_cache, counters):
         cfg = self.cfg
         B, _, d = emb.shape
-        H, D = cfg.num_attention_heads, cfg.head_dim
+        H, D, E, k = cfg.num_attention_heads, cfg.head_dim, cfg.num_experts, cfg.top_k_experts
         x = emb.reshape(B, d)
         self.gate_pass += 1
         fold = ops.gemv_rmsnorm_ok(B, d, head_dim=D, swiglu_n=2 * cfg.intermediate_size)   # input_layernorm inside the qkv GEMV (same bits, one launch less per layer)
@@ -448,29 +459,23 @@ class LlamaStack:
             q4 = qkv.view(B, 1, 3, H, D)[:, :, 0]
             attn = ops.attention(q4, kv_cache["k"][i], kv_cache["v"][i], causal=False, sk_dev=counters[1:2])
             x = ops.gemv(attn.view(B, d), lw["o"], residual=x)
-            if (i in self.moe_layers and cfg.top_k_experts == 1 and self.ep is None and B <= 8 and self.fuse_decode_routing
-                    and not cfg.use_residual):
-                # post-attention norm + gate + routing in one launch, then the two expert GEMVs (same bits as the separate kernels)
-                E, cap = cfg.num_experts, self.capacity(B)
-                draws = None if cap >= B else self._gate_draws(i, B, E, gumbel=False)
-                h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
-                act = ops.gemv(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR, w_index=expert)
-                x = ops.gemv(act, lw["down"], residual=x, w_index=expert, row_scale=weight, row_keep=slot)
-            elif (i in self.moe_layers and cfg.top_k_experts == 2 and self.ep is None and B <= 8 and self.fuse_decode_routing
-                    and not cfg.use_residual):
-                # top-2: norm + gate + routing in one launch, then the two-expert GEMVs (the bits of _mlp's decode-row top-2 branch)
-                E, cap = cfg.num_experts, self.capacity(B)
-                h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route_top2(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap,
-                                                                                   self._gate_draws(i, B, E, gumbel=True))
-                act = ops.gemv_top2_gate_up(h, lw["gu"], expert, slot)
-                x = ops.gemv_top2_down(act, lw["down"], expert, slot, weight, x)
+            # post-attention norm + gate + routing in ONE launch, then the expert GEMVs of _mlp's decode-row branches (the separate kernels' bits)
+            if i in self.moe_layers and self.fuse_decode_routing and self._expert_gemv_rows(B) and k in (1, 2):
+                cap = self.capacity(B)
+                if k == 1:
+                    draws = None if cap >= B else self._gate_draws(i, B, E, False, pass_dev)
+                    h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
+                    x = self._expert_gemvs_top1(lw, h, x, expert, slot, weight)
+                else:
+                    draws = self._gate_draws(i, B, E, True, pass_dev)
+                    h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route_top2(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
+                    x = self._expert_gemvs_top2(lw, h, x, expert, slot, weight)
             elif fold and i not in self.moe_layers:
                 # dense layer: post_attention_layernorm inside the gate|up GEMV (same bits as rmsnorm + gemv), then the down projection
                 act = ops.gemv_rmsnorm(x, lw["ln2"], cfg.rms_norm_eps, lw["gu"], act=ops.ACT_SWIGLU_PAIR)
                 x = ops.gemv(act, lw["down"], residual=x)
             else:
-                h = ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps)
-                x, _, _ = self._mlp(i, lw, h, x)
+                x, _, _ = self._mlp(i, lw, ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps), x, pass_dev=pass_dev)
         return ops.rmsnorm(x, self.norm_w, cfg.rms_norm_eps).view(B, 1, d)
 
     def next_token_logits(self, hidden_row):

@@ -603,6 +603,42 @@ def _moe_bwd(llm, lora, i, lw, s, dx, d_aux, grads, take_e):
     return d_h2
 
 
+def _dense_mlp_fwd(llm, lora, lw, pad, s, seed, h2, gu_ext, x_mid, rows=None):
+    """x_mid + down(silu(gate) * up) of a dense layer with its adapters, leaving in `s` what the backward reads.  h2 [T, d] = the normed rows,
+    gu_ext = (the [T, d + 64] buffer h2 lives in, its adapter part) when gate|up carries adapters.  rows (int64 [n]): the MLP runs on compact
+    copies of those rows only and its result is scattered back into x_mid, which is returned."""
+    d, ff, dev = llm.cfg.hidden_size, llm.cfg.intermediate_size, x_mid.device
+    if rows is not None and gu_ext is not None:
+        h2x, h2_c, t3 = _ext_rows(rows.numel(), d, dev)
+        ops.gather_rows_bf16(h2, rows, out=h2_c)
+        h2, gu_ext = h2_c, (h2x, t3)
+    elif rows is not None:
+        h2 = ops.gather_rows_bf16(h2, rows)
+    actx, act, t4 = _ext_rows(h2.shape[0], ff, dev) if "down_x" in lw else (None, None, None)
+    if gu_ext is not None:
+        s["h2d"], s["t_gu"] = _adapter_down(lora, pad["gu"], h2, gu_ext[1], seed), gu_ext[1]
+        gin, gw = gu_ext[0], lw["gu_x"]
+    else:
+        gin, gw = h2, lw["gu"]
+    # gate|up: silu(gate) * up from the GEMM's epilogue, which also stores the gate|up values the backward reads
+    if _SWIGLU_KEEP:
+        act, gu = ops.gemm_swiglu_keep(gin, gw, act_out=act)
+    else:                                                  # A/B: the two-kernel form
+        gu = ops.gemm(gin, gw)
+        act = ops.swiglu_pair_fwd(gu, out=act)
+    res = x_mid if rows is None else ops.gather_rows_bf16(x_mid, rows)
+    if "down_x" in lw:
+        s["actd"], s["t_d"] = _adapter_down(lora, pad["down"], act, t4, seed + 1), t4
+        out = ops.gemm(actx, lw["down_x"], residual=res)
+    else:
+        out = ops.gemm(act, lw["down"], residual=res)
+    s["gu"] = gu
+    if rows is None:
+        return out
+    s.update(rows_last=rows, xm_c=res, x_mid=None)
+    return ops.scatter_rows_bf16_(x_mid, rows, out)
+
+
 def forward_train(llm, embeds, key_valid):
     """The decoder forward in training-with-adapters mode -> (last_hidden [B,S,d], saved)."""
     cfg, lora = llm.cfg, llm.lora
@@ -618,7 +654,7 @@ def forward_train(llm, embeds, key_valid):
         pack_all(lora, len(llm.layers))
     llm.gate_pass += 1
     saved, aux = [], []
-    needed = getattr(llm, "needed_rows", None)                  # (rows int64, mask uint8) of the output rows something reads, or None
+    needed = llm.needed_rows                                    # (rows int64, mask uint8) of the output rows something reads, or None
     if needed is not None and needed[1].numel() != T:
         needed = None
     for i, lw in enumerate(llm.layers):
@@ -656,56 +692,15 @@ def forward_train(llm, embeds, key_valid):
         if i in llm.moe_layers:
             x_out, l_aux = (_moe_fwd_ep if llm.ep is not None else _moe_fwd)(llm, lora, i, lw, pad, h2, x_mid, s, seed)
             aux.append(l_aux)
-        elif (_PRUNE_ROWS and needed is not None and i == len(llm.layers) - 1 and _SWIGLU_KEEP and (i, "ln2") not in lora.norm_names):
+        else:
             # The LAST layer's MLP on the rows something reads (model_forward: supervised rows + <SEG> rows, ~1 % of the tokens): the MLP is
             # row-wise, every read row gets the result of the same arithmetic on a compact [n, d] tensor (the lora_dropout mask is a function of
             # the position inside the tensor it is drawn for, so it is another sample of the same distribution than the full-size pass would
             # have drawn; forward and backward use the same one).  x_mid's read rows are replaced in place: it becomes this layer's output.
-            rows = needed[0]
-            n_r = rows.numel()
-            llm.pruned_rows = int(n_r)                              # the pruning HAPPENED (model_forward reports only this)
-            if "gu_x" in lw:
-                h2x_c, h2_c, t3_c = _ext_rows(n_r, d, x.device)
-                ops.gather_rows_bf16(h2, rows, out=h2_c)
-                s["h2d"], s["t_gu"] = _adapter_down(lora, pad["gu"], h2_c, t3_c, seed), t3_c
-                gin, gw = h2x_c, lw["gu_x"]
-            else:
-                gin, gw = ops.gather_rows_bf16(h2, rows), lw["gu"]
-            if "down_x" in lw:
-                actx, act, t4 = _ext_rows(n_r, cfg.intermediate_size, x.device)
-            else:
-                act = None
-            act, gu = ops.gemm_swiglu_keep(gin, gw, act_out=act)
-            xm_c = ops.gather_rows_bf16(x_mid, rows)
-            if "down_x" in lw:
-                s["actd"], s["t_d"] = _adapter_down(lora, pad["down"], act, t4, seed + 1), t4
-                out_c = ops.gemm(actx, lw["down_x"], residual=xm_c)
-            else:
-                out_c = ops.gemm(act, lw["down"], residual=xm_c)
-            x_out = ops.scatter_rows_bf16_(x_mid, rows, out_c)
-            s.update(gu=gu, rows_last=rows, xm_c=xm_c, x_mid=None)
-        else:
-            # gate|up: silu(gate) * up from the GEMM's epilogue, which also stores the gate|up values the backward reads
-            if "down_x" in lw:
-                actx, act, t4 = _ext_rows(T, cfg.intermediate_size, x.device)
-            else:
-                act = None
-            if "gu_x" in lw:
-                s["h2d"], s["t_gu"] = _adapter_down(lora, pad["gu"], h2, t3, seed), t3
-                gin, gw = h2x, lw["gu_x"]
-            else:
-                gin, gw = h2, lw["gu"]
-            if _SWIGLU_KEEP:
-                act, gu = ops.gemm_swiglu_keep(gin, gw, act_out=act)
-            else:                                                  # A/B: the two-kernel form
-                gu = ops.gemm(gin, gw)
-                act = ops.swiglu_pair_fwd(gu, out=act)
-            if "down_x" in lw:
-                s["actd"], s["t_d"] = _adapter_down(lora, pad["down"], act, t4, seed + 1), t4
-                x_out = ops.gemm(actx, lw["down_x"], residual=x_mid)
-            else:
-                x_out = ops.gemm(act, lw["down"], residual=x_mid)
-            s["gu"] = gu
+            prune = _PRUNE_ROWS and needed is not None and i == len(llm.layers) - 1 and _SWIGLU_KEEP and (i, "ln2") not in lora.norm_names
+            if prune:
+                llm.pruned_rows = int(needed[0].numel())                # the pruning HAPPENED (model_forward reports only this)
+            x_out = _dense_mlp_fwd(llm, lora, lw, pad, s, seed, h2, (h2x, t3) if "gu_x" in lw else None, x_mid, rows=needed[0] if prune else None)
         saved.append(s)
         x = x_out
     out = ops.rmsnorm(x, llm.norm_w, cfg.rms_norm_eps)

@@ -549,19 +549,19 @@ class MedPLIBForCausalLM(nn.Module):
         # launches (windowed attention, adapter convolutions on 64-token maps) fill in beside the LLM's GEMMs instead of
         # occupying the machine alone.  Joined again before the mask tail.
         image_tokens = None
-        lo_ = getattr(m.llm, "lora", None)
+        lo_ = m.llm.lora
         front_frozen = lo_ is None or not any(n.startswith(("model.mm_projector.", "model.mm_token_compressor.", "model.region_fea_adapter.",
                                                              "model.mask_encoder.")) for n in lo_.names)
         ahead = (self.towers_run_ahead and front_frozen and not getattr(self, "_want_raw_feats", False)
                  and not (region_masks is not None and len(region_masks) > 0) and kwargs.get("mask_images") is None and torch.is_tensor(images_clip))
         # Towers that run ahead are issued BEFORE this step's decoder, i.e. while the device is still inside the PREVIOUS step's decoder: with
         # gate_towers on, layer j of the CLIP tower / block k of the SAM encoder waits for the event the previous step's decoder recorded where
-        # its layer j / 32 - 12 + k started its expert GEMMs (llama._mlp) — the gate|up launch (5.71 waves of tiles: dynamic, with slack in its last
+        # its layer j / 32 - 12 + k started its expert GEMMs (llama._mlp_gather_scatter) — the gate|up launch (5.71 waves of tiles: dynamic, with slack in its last
         # wave) absorbs side workgroups, the exact-wave qkv / o_proj launches (768 / 256 tiles on 256 CUs) end late by whatever a side workgroup
         # still holds a CU for at their start.  Events already complete (first step, a host that is not ahead) gate nothing.
         n_l = len(m.llm.layers)
         gate_on = bool(ahead and getattr(self, "gate_towers", _GATE_TOWERS) and cfg.moe_enable and n_l >= 24 and self.training and not inference)
-        if gate_on and getattr(m.llm, "layer_events", None) is None:
+        if gate_on and m.llm.layer_events is None:
             m.llm.layer_events = [torch.cuda.Event() for _ in range(n_l)]
             for e_ in m.llm.layer_events:
                 e_.record()                                  # so that the first step's waits see a completed record
@@ -619,12 +619,12 @@ class MedPLIBForCausalLM(nn.Module):
                     m.llm.needed_rows = (_h2d(need, dev), _h2d(mask, dev))
             exp = self.expand_index(valid_mask_bool, B) if seg_flag else None
             exp_d = _h2d(np.asarray(exp, dtype=np.int64), dev) if (seg_flag and exp != list(range(B))) else None
-            if getattr(m.llm, "lora", None) is not None:
+            if m.llm.lora is not None:
                 m.llm.lora.sync_model(m.llm)                        # bf16 working copies of lm_head / embed_tokens when they train
             embeds = ops.splice_rows(m.llm.embed_tokens, feats, src, cfg.hidden_size).view(B, plan.seq_len, cfg.hidden_size)
             # adapters attached: they act in every forward of this method (training, validation, inference masks) like a peft
             # model; the KV-cache decode paths want them merged (merge_and_unload())
-            lora_train = getattr(m.llm, "lora", None) is not None
+            lora_train = m.llm.lora is not None
             if not lora_train:
                 last_hidden, aux, self._routing = m.llm.forward(embeds, key_valid, collect_routing=self.capture_intermediates)
                 ce = m.llm.cross_entropy(last_hidden, sup_rows_d, sup_labels_d, aux)
@@ -637,7 +637,7 @@ class MedPLIBForCausalLM(nn.Module):
                 last_hidden, aux_sum, _ = LL.forward_train(m.llm, embeds, key_valid)
                 ce = m.llm.cross_entropy(last_hidden, sup_rows_d, sup_labels_d, [aux_sum] if m.llm.moe_layers else [])
         # the row set belonged to THIS pass through the stack: a later direct call of the stack (evaluate(), a test) computes every row
-        nr, done = m.llm.needed_rows, getattr(m.llm, "pruned_rows", None)
+        nr, done = m.llm.needed_rows, m.llm.pruned_rows
         # (rows the last layer's MLP ran on, rows of the batch) when the stack really pruned (top-1 fused-gate MoE branch / dense last layer with
         # frozen ln2 under adapters: it records llm.pruned_rows), else None — bench.py reports and subtracts FLOPs only from this
         self.last_pruned = (int(done), int(nr[1].numel())) if (nr is not None and done is not None) else None
