@@ -946,7 +946,8 @@ def sgemm(a, b, trans_a=False, trans_b=False, bias=None, act=SACT_NONE, alpha=1.
     the innermost stride is 1."""
     _chk(a, torch.float32, "sgemm.a"); _chk(b, torch.float32, "sgemm.b")
     nb = a.dim() - 2
-    assert b.dim() == a.dim() and nb in (0, 1, 2) and a.stride(-1) == 1 and b.stride(-1) == 1
+    # a last dimension of size 1 may carry any stride (torch keeps the transposed one through .contiguous()): nothing steps along it
+    assert b.dim() == a.dim() and nb in (0, 1, 2) and (a.stride(-1) == 1 or a.shape[-1] == 1) and (b.stride(-1) == 1 or b.shape[-1] == 1)
     am, ak = (a.shape[-1], a.shape[-2]) if trans_a else (a.shape[-2], a.shape[-1])
     bk, bn = (b.shape[-1], b.shape[-2]) if trans_b else (b.shape[-2], b.shape[-1])
     assert ak == bk, f"sgemm: inner dims differ {ak} vs {bk}"

@@ -1,5 +1,6 @@
-"""Helpers shared by the kernel-level parity tests (test_gpu_train_kernels.py, test_gpu_glue_kernels.py, test_gpu_attention_edges.py)
-and the crafted MoE routing cases their CPU guard checks (test_kernel_coverage.py).  Plain torch on the CPU only: nothing here touches the GPU."""
+"""Helpers shared by the kernel-level parity tests (test_gpu_train_kernels.py, test_gpu_glue_kernels.py, test_gpu_attention_edges.py,
+test_gpu_row_kernels.py, test_gpu_f32_tail_kernels.py), the crafted MoE routing cases their CPU guard checks (test_kernel_coverage.py)
+and the crafted row-kernel inputs (test_row_kernel_cases.py).  Plain torch on the CPU only: nothing here touches the GPU."""
 import torch
 
 U32 = 2.0 ** -24          # unit roundoff of fp32 (half an ulp, relative)
@@ -280,3 +281,322 @@ def attn_bwd_ref_and_tols(q, k, v, d_out, allowed, scale, c_fwd, lse_tol, A):
         + (u + U32) * k64.grad.abs() + tiny
     tol_dv = (2 * u + u * u + eps_p + Sq * U32) * torch.einsum("bhqk,bqhd->bkhd", P, g.abs()) + tiny
     return {"dq": q64.grad, "dk": k64.grad, "dv": v64.grad, "tol_dq": tol_dq, "tol_dk": tol_dk, "tol_dv": tol_dv}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Row, elementwise and fp32 tail kernels (tests/test_gpu_row_kernels.py, tests/test_gpu_f32_tail_kernels.py) and the CPU guard of
+# their crafted inputs (tests/test_row_kernel_cases.py).  u = U_BF16 = 2^-8, U32 = 2^-24.  The device math functions (rsqrtf, sqrtf,
+# the fp32 division, expf, __expf, erff, v_rcp_f32) are ASSUMED good to 2 ulp = 4 U32 (profiles/kernel_parity_tests.md); everything
+# else in the bounds below counts roundings read off the kernels.
+ULP2 = 4 * U32
+CANARY = -7.5            # exact in bf16 and fp32; no kernel here produces a whole band of it
+
+
+def gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def canary_view(rows, cols, ld, dtype, dev, lead=8):
+    """(whole, view): a [rows, cols] view with row stride ld inside a buffer filled with CANARY, `lead` elements in front of the
+    first row and a whole spare row behind the last one (lead a multiple of 8 keeps 16-byte alignment for bf16)."""
+    whole = torch.full((lead + (rows + 1) * ld,), CANARY, dtype=dtype, device=dev)
+    return whole, whole[lead:lead + rows * ld].view(rows, ld)[:, :cols]
+
+
+def canary_intact(name, whole, rows, cols, ld, lead=8):
+    """Everything of `whole` outside the [rows, cols] view still holds CANARY's bits."""
+    w = whole.detach().cpu()
+    keep = torch.ones(w.numel(), dtype=torch.bool)
+    keep[lead:lead + rows * ld].view(rows, ld)[:, :cols] = False
+    ref = torch.full_like(w, CANARY)
+    n = int((bits(w)[keep] != bits(ref)[keep]).sum())
+    print(f"{name}: {n}/{int(keep.sum())} canary elements changed")
+    assert n == 0, f"{name}: {n} elements outside the output view were written"
+
+
+def strided_in(t, ld, dev, lead=8):
+    """The CPU tensor t [rows, cols] on the device as a view with row stride ld (CANARY in the gaps)."""
+    whole, v = canary_view(t.shape[0], t.shape[1], ld, t.dtype, dev, lead)
+    v.copy_(t.to(dev))
+    return v
+
+
+def bf16_ulp(x):
+    """Spacing of bf16 at |x| (float64 tensor): 2^(e - 7), the subnormal spacing 2^-133 below 2^-126."""
+    e = torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -126)))
+    return torch.pow(torch.tensor(2.0, dtype=torch.float64), e - 7)
+
+
+def bf16_flip_slack(t64, rel):
+    """(bf16(t64) as float64, slack): slack = the distance between the two bf16 values that t64 (1 +- rel) round to: zero unless t64 is
+    within rel |t64| of a rounding boundary, where a kernel whose fp32 value is off by that much may land on the neighbour."""
+    lo, hi = bf((t64 * (1 - rel)).float()).double(), bf((t64 * (1 + rel)).float()).double()
+    return bf(t64.float()).double(), (hi - lo).abs()
+
+
+# RMSNorm (rmsnorm_bf16_kernel), HF order: t = bf16(x * rs), y = bf16(w * t).
+#   ss = sum x^2: dim products and a sum of dim terms in any order: relative (dim + 1) U32 (all terms >= 0); / dim and + eps: 2 U32;
+#   rsqrtf halves the relative error of its argument and adds ULP2: e_rs = ((dim + 3) / 2 + 4) U32; x * rs: one more U32.
+#   Where x rs64 is within (e_rs + U32) of a bf16 rounding boundary, t may be the neighbouring bf16 value (bf16_flip_slack); elsewhere
+#   t is the reference's.  y = bf16(fl32(w t)): u |w t| (1 + U32) + U32 |w t| <= (u + 2 U32) |w t|.
+#   bound = (u + 2 U32) |w t_ref| + (1 + u) |w| slack
+def rmsnorm_ref(x, w, eps):
+    """x bf16 [rows, dim], w fp32 [dim] (CPU) -> (ref float64 = w * bf16(x rs), bound)."""
+    x64, w64 = x.double(), w.double()
+    dim = x.shape[-1]
+    rs = torch.rsqrt((x64 * x64).mean(-1, keepdim=True) + eps)
+    e_rs = ((dim + 3) / 2 + 4) * U32
+    t, slack = bf16_flip_slack(x64 * rs, e_rs + U32)
+    ref = w64 * t
+    return ref, (U_BF16 + 2 * U32) * ref.abs() + (1 + U_BF16) * w64.abs() * slack
+
+
+# LayerNorm.  Shared first-order analysis of y = (x - mean) rs w + b with fp32 statistics in two passes; `depth` = the longest chain
+# of additions one element goes through in the kernel's sum (lane-sequential part + 6 shuffle levels [+ the waves of the block form]),
+# so |fl(sum) - sum| <= depth U32 sum|.| whatever the values; sum_exact=True (inputs whose every partial sum is exactly representable:
+# the offset and constant rows, proved by tests/test_row_kernel_cases.py) leaves only the division's rounding.
+#   dm   = depth U32 mean|x| + U32 |mean|                                 error of the mean
+#   d    = x - mean: |err| <= dm + U32 |d|
+#   dvar = 2 mean|d| dm + dm^2 + (depth + 3) U32 var                      (d^2: 2 |d| err + err^2; dim products, the sum, the division)
+#   e_rs = dvar / (2 (var + eps)) + U32 + e_root     (+ eps: one rounding; the root: `e_root` = ULP2 for rsqrtf, 2 ULP2 for 1 / sqrtf)
+#   E    = |w| rs (dm + U32 |d|) + |d rs w| (e_rs + 3 U32) + 2 U32 (|d rs w| + |b|)       error of the fp32 value before the store
+def layernorm_ref(x, w, b, eps, depth, sum_exact=False, e_root=ULP2):
+    """x [rows, dim] (any float dtype, CPU), w, b fp32 or None -> dict(y, mean, rstd, E, dm, e_rs) in float64."""
+    x64 = x.double()
+    w64 = w.double()
+    b64 = torch.zeros_like(w64) if b is None else b.double()
+    mean = x64.mean(-1, keepdim=True)
+    d = x64 - mean
+    var = (d * d).mean(-1, keepdim=True)
+    rs = torch.rsqrt(var + eps)
+    dm = (0.0 if sum_exact else depth * U32) * x64.abs().mean(-1, keepdim=True) + U32 * mean.abs()
+    dvar = 2 * d.abs().mean(-1, keepdim=True) * dm + dm * dm + (depth + 3) * U32 * var
+    e_rs = dvar / (2 * (var + eps)) + U32 + e_root
+    core = (d * rs * w64).abs()
+    E = w64.abs() * rs * (dm + U32 * d.abs()) + core * (e_rs + 3 * U32) + 2 * U32 * (core + b64.abs())
+    return {"y": d * rs * w64 + b64, "mean": mean.squeeze(-1), "rstd": rs.squeeze(-1), "E": E, "dm": dm.squeeze(-1), "e_rs": e_rs.squeeze(-1)}
+
+
+def layernorm_bf16_bound(r):
+    """The bf16 store of a value that is off by E: u (|y| + E) + E."""
+    return U_BF16 * (r["y"].abs() + r["E"]) + r["E"]
+
+
+LN_BF16_DEPTH = 32 + 6 + 4      # <= 4 chunks of 8 per lane, 6 shuffle levels, 4 waves summed in order (the block form)
+
+
+def ln_f32_depth(dim):
+    return -(-dim // 64) + 6
+
+
+def offset_rows_bf16(rows, dim, seed):
+    """Rows with mean ~100 and a spread of one bf16 step (0.5 at 100): values in {99.5, 100, 100.5}.  Every partial sum is a multiple
+    of 0.5 below 2^23, hence exact in fp32 in any order."""
+    return (100.0 + 0.5 * (torch.randint(0, 3, (rows, dim), generator=gen(seed)) - 1).float()).bfloat16()
+
+
+def offset_rows_f32(rows, dim, seed):
+    """fp32 rows with mean 1e3 and spread 1e-2."""
+    return (1e3 + 1e-2 * torch.randn(rows, dim, generator=gen(seed), dtype=torch.float64)).float()
+
+
+# LayerNorm backward (ln_bwd_f32_kernel) from the kernel's own fp32 mean / rstd (the reference reads the same values):
+#   xh = (x - mu) rs: 2 U32 |xh|; g = dy w: U32 |g|; sg = mean(g), sgx = mean(g xh): depth-long sums
+#   dsg = (depth + 2) U32 mean|g|, dsgx = (depth + 5) U32 mean|g xh|
+#   dx = rs (g - sg - xh sgx): bound = rs (dsg + |xh| dsgx + 6 U32 (|g| + |sg| + |xh sgx|)) + U32 |dx|
+def layernorm_bwd_ref(dy, x, w, mean, rstd):
+    dy64, x64, w64 = dy.double(), x.double(), w.double()
+    dim = x.shape[-1]
+    depth = ln_f32_depth(dim)
+    mu, rs = mean.double()[:, None], rstd.double()[:, None]
+    xh = (x64 - mu) * rs
+    g = dy64 * w64
+    sg, sgx = g.mean(-1, keepdim=True), (g * xh).mean(-1, keepdim=True)
+    dx = rs * (g - sg - xh * sgx)
+    dsg = (depth + 2) * U32 * g.abs().mean(-1, keepdim=True)
+    dsgx = (depth + 5) * U32 * (g * xh).abs().mean(-1, keepdim=True)
+    bound = rs * (dsg + xh.abs() * dsgx + 6 * U32 * (g.abs() + sg.abs() + (xh * sgx).abs())) + U32 * dx.abs()
+    # dw / db (ln_bwd_wb_f32_kernel): ceil(rows / 16) sequential terms per wave, 16 partials in order, the += : chain length below
+    rows = x.shape[0]
+    chain = -(-rows // 16) + 16 + 1
+    tw, tb = (dy64 * xh).sum(0), dy64.sum(0)
+    bw = (chain + 3) * U32 * (dy64 * xh).abs().sum(0)
+    bb = chain * U32 * dy64.abs().sum(0)
+    return {"dx": dx, "dx_bound": bound, "dw": tw, "dw_bound": bw, "db": tb, "db_bound": bb}
+
+
+# Softmax forward (softmax_fwd_f32_kernel): p = expf(s x - m) / sum.  A = max |s x|.
+#   exponent: fl(s x) and m = the largest fl(s x) are each off by U32 A, the subtraction by U32 * 2A: absolute 4 U32 A = relative e_s
+#   of p; expf ULP2; the sum of depth-long chains; 1 / sum ULP2; the product U32.  The error of the normaliser is common to the row.
+#   c = 2 (e_s + ULP2) + (depth + 1) U32 + ULP2 + U32;  floor 2^-125: a term or a result below 2^-126 may be flushed
+def softmax_ref(x, scale):
+    x64 = x.double() * scale
+    p = torch.softmax(x64, -1)
+    fin = torch.where(torch.isfinite(x64), x64, torch.zeros_like(x64))
+    A = fin.abs().amax(-1, keepdim=True)
+    c = 2 * (4 * U32 * A + ULP2) + (ln_f32_depth(x.shape[-1]) + 2) * U32 + ULP2
+    bound = torch.where(p > 0, c * p + 2.0 ** -125, torch.zeros_like(p))
+    return p, bound, c.squeeze(-1)
+
+
+# Softmax backward: dx = s p (dp - sum(p dp)):  the sum: (depth + 1) U32 sum|p dp|; the difference and two products: 3 roundings;
+# floor 2^-125 where p > 0: a product below 2^-126 is subnormal or flushed (p = 0 gives an exact zero)
+def softmax_bwd_ref(p, dp, scale):
+    p64, dp64 = p.double(), dp.double()
+    s = (p64 * dp64).sum(-1, keepdim=True)
+    ds = (ln_f32_depth(p.shape[-1]) + 1) * U32 * (p64 * dp64).abs().sum(-1, keepdim=True)
+    dx = scale * p64 * (dp64 - s)
+    return dx, abs(scale) * p64 * (ds + 2 * U32 * (dp64.abs() + s.abs())) + 3 * U32 * dx.abs() + 2.0 ** -125 * (p64 > 0)
+
+
+def softmax_case(kind, rows, cols, seed):
+    g = gen(seed)
+    if kind == "random":
+        return 3 * torch.randn(rows, cols, generator=g)
+    if kind == "equal":
+        return torch.full((rows, cols), 1.25) * torch.arange(1, rows + 1).float()[:, None]
+    if kind == "spread":            # +-1e4: all but the few entries next to the maximum underflow
+        x = (torch.rand(rows, cols, generator=g) * 2 - 1) * 1e4
+        x[:, 0] = 1e4
+        x[:, -1] = -1e4 if cols > 1 else 1e4
+        return x
+    if kind == "neginf":            # every other entry -inf beside finite ones (entry 0 stays finite)
+        x = torch.randn(rows, cols, generator=g)
+        x[:, 1::2] = float("-inf")
+        return x
+    raise ValueError(kind)
+
+
+# exact erf GELU in fp32 (gelu_erf): y = 0.5 x (1 + erff(z)), z = fl(x * fl(1/sqrt2)).
+#   erf: ULP2 |erf| + 2 U32 |z| erf'(z) (the constant's and the product's rounding of the argument);  1 + erf: U32 |1 + erf|
+#   y: 0.5 |x| (that) + 2 U32 |y|.  For x << 0 the sum 1 + erf cancels: the bound there is absolute, ~ |x| ULP2 / 2.
+def _erf_parts(x64):
+    z = x64 * 0.7071067811865476
+    erf = torch.erf(z)
+    derf = 1.1283791670955126 * torch.exp(-z * z)
+    e_sum = ULP2 * erf.abs() + 2 * U32 * z.abs() * derf + U32 * (1 + erf).abs()
+    return erf, e_sum
+
+
+def gelu_ref(x, dv=None):
+    """float64 GELU of x and its bound; dv = an error the INPUT already carries (the sgemm epilogue): |gelu'| <= 1.13."""
+    x64 = x.double()
+    erf, e_sum = _erf_parts(x64)
+    y = 0.5 * x64 * (1 + erf)
+    bound = 0.5 * x64.abs() * e_sum + 2 * U32 * y.abs()
+    if dv is not None:
+        bound = bound + 1.13 * dv * (1 + ULP2)
+    return y, bound
+
+
+# GELU derivative (gelu_erf_grad): cdf + x pdf, pdf = c __expf(a), a = -0.5 x^2.
+#   a: 2 U32 |a|; __expf multiplies by log2(e) (constant and product: 2 U32 |a log2e|) before v_exp: relative 4 U32 |a| + ULP2; c *: U32
+#   cdf: 0.5 e_sum + U32 cdf; x pdf and the sum: 2 U32 |grad| ; dy *: U32
+def gelu_grad_ref(dy, x):
+    dy64, x64 = dy.double(), x.double()
+    erf, e_sum = _erf_parts(x64)
+    cdf = 0.5 * (1 + erf)
+    pdf = 0.3989422804014327 * torch.exp(-0.5 * x64 * x64)
+    grad = cdf + x64 * pdf
+    e_pdf = (4 * 0.5 * x64 * x64 + 2) * U32 + ULP2
+    e = 0.5 * e_sum + U32 * cdf.abs() + (x64 * pdf).abs() * (e_pdf + U32) + 2 * U32 * (cdf.abs() + (x64 * pdf).abs())
+    ref = dy64 * grad
+    return ref, dy64.abs() * e + U32 * ref.abs()
+
+
+# SwiGLU (swiglu_bf16_kernel): bf16(g * mp_sigmoid_fast(g) * u).  ASSERTED: one bf16 ulp of the exact value plus a floor.  The floor:
+# 1 + __expf(-g) exceeds 2^126 for g < -126 ln 2 = -87.34, its reciprocal is then subnormal and v_rcp_f32 returns 0 (for g < -88.7
+# __expf overflows and rcp(inf) = 0): the kernel gives -0 where the exact |silu(g)| = |g| e^g <= 87.34 * 2^-126 (|g| e^g falls with
+# |g| beyond 1).  Times |u|, plus 2^-126 for a product that is itself subnormal.
+def swiglu_ref(gv, uv):
+    g64, u64 = gv.double(), uv.double()
+    ref = g64 * torch.sigmoid(g64) * u64
+    floor = 87.34 * 2.0 ** -126 * u64.abs() + 2.0 ** -126
+    return ref, bf16_ulp(ref), floor
+
+
+def swiglu_sweep():
+    """gu [3, 2F] bf16: every finite bf16 g in [-100, 100] (zero padded to a multiple of 8) against u = 1, -1.5, 3e4, one per row."""
+    pat = torch.arange(0, 65536, dtype=torch.int32).to(torch.int16).view(torch.bfloat16)
+    g = pat[torch.isfinite(pat.float()) & (pat.float().abs() <= 100)]
+    F = (g.numel() + 7) // 8 * 8
+    gu = torch.zeros(3, 2 * F, dtype=torch.bfloat16)
+    gu[:, :g.numel()] = g
+    for r, u in enumerate((1.0, -1.5, 3e4)):
+        gu[r, F:] = u
+    return gu, g.numel()
+
+
+# RoPE (rope_qk_bf16_kernel, decode_rope_append_kernel): lo' = bf16(a cos - b sin), hi' = bf16(b cos + a sin) in fp32: two products
+# and a sum (or a product and an fma): <= 3 U32 (|a cos| + |b sin|), then the store.
+def rope_ref(lo, hi, cos, sin):
+    """float64 halves [..., half] and tables broadcastable to them -> (lo', hi', bound_lo, bound_hi)."""
+    rl, rh = lo * cos - hi * sin, hi * cos + lo * sin
+    el, eh = 3 * U32 * ((lo * cos).abs() + (hi * sin).abs()), 3 * U32 * ((hi * cos).abs() + (lo * sin).abs())
+    return rl, rh, U_BF16 * (rl.abs() + el) + el, U_BF16 * (rh.abs() + eh) + eh
+
+
+# cast_to_bf16: the fp32 values around every rounding tie.
+def cast_tie_sweep():
+    """fp32 [3 * 65280 + specials + 8]: for every finite bf16 pattern p the exact midpoint between p and its successor in magnitude
+    (fp32 bits p << 16 | 0x8000) and the fp32 values one ulp to either side; +-0, +-inf, NaNs, fp32 subnormals, the largest finite
+    fp32; and eight ties (both parities of p) at the very end, so that a length cut by 0..3 still ends on ties."""
+    p = torch.arange(0, 65536, dtype=torch.int64)
+    p = p[(p & 0x7F80) != 0x7F80]                                   # finite bf16 patterns, both signs
+    mid = (p << 16) | 0x8000
+    body = torch.stack([mid - 1, mid, mid + 1], 1).reshape(-1)
+    special = torch.tensor([0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00000, 0x7F800001, 0x7FC12345, 0xFFFFFFFF,
+                            0x7F80FFFF, 0x00000001, 0x80000001, 0x007FFFFF, 0x00008000, 0x00018000, 0x7F7FFFFF, 0xFF7FFFFF], dtype=torch.int64)
+    tail = torch.tensor([0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000, 0x40008000, 0x40018000, 0x00808000, 0x00818000], dtype=torch.int64)
+    allb = torch.cat([body, special, tail])
+    allb = torch.where(allb >= 2 ** 31, allb - 2 ** 32, allb).to(torch.int32)
+    return allb.view(torch.float32)
+
+
+def assert_bits_nan(name, got, ref):
+    """Equal bits, except that a NaN matches any NaN."""
+    g, r = got.detach().cpu(), ref.detach().cpu()
+    gn, rn = torch.isnan(g.float()), torch.isnan(r.float())
+    diff = (bits(g) != bits(r)) & ~(gn & rn)
+    n = int(diff.sum())
+    first = int(diff.flatten().nonzero()[0]) if n else -1
+    msg = f"{name}: {n}/{g.numel()} elements differ (NaN matches NaN)" + (f", first at {first}: got bits {int(bits(g).flatten()[first]) & 0xFFFFFFFF:#x}, "
+                                                                          f"expected {int(bits(r).flatten()[first]) & 0xFFFFFFFF:#x}" if n else "")
+    print(msg)
+    assert n == 0, msg
+
+
+# Integer-valued operands: |a|, |b| <= 8 and K <= 4096 keep every partial sum of products below 64 * 4096 = 2^18 < 2^24, so fp32
+# sums are exact in any order (sgemm, colsum, the atomic split-K) and must equal float64 bit for bit.
+def int_values(shape, seed, lim=8):
+    return torch.randint(-lim, lim + 1, shape, generator=gen(seed)).float()
+
+
+SGEMM_MN = (1, 63, 64, 65, 129)
+SGEMM_K = (1, 15, 16, 17, 63, 64, 65, 130)
+
+
+def sgemm_cases():
+    """[(form, M, N, K)]: per operand form every K once, every M and every N at least once (not the cross product), plus the K = 63 / 64
+    pair at one ragged (M, N): the 16-deep kernel runs below k_unit = 64, the 64-deep one from there."""
+    out = []
+    for f, form in enumerate(("NN", "NT", "TN")):
+        for i, K in enumerate(SGEMM_K):
+            out.append((form, SGEMM_MN[(i + f) % 5], SGEMM_MN[(2 * i + f + 1) % 5], K))
+        out += [(form, 65, 65, 63), (form, 65, 65, 64)]
+    return out
+
+
+def sgemm_operands(form, M, N, K, seed, batch=()):
+    """Integer-valued (a, b) as STORED for the form, and the float64 product."""
+    a, b = int_values(batch + (M, K), seed), int_values(batch + (K, N), seed + 1)
+    ref = a.double() @ b.double() + 0.0          # + 0.0: a K = 1 product 0 * -3 is -0 in the library's float64 GEMM; the kernel's fma chain starts at +0
+    if form == "NT":
+        b = b.transpose(-1, -2).contiguous()
+    if form == "TN":
+        a = a.transpose(-1, -2).contiguous()
+    return a, b, ref
+
+
+COLSUM_ROWS = (0, 1, 15, 16, 17, 48, 49, 63, 64, 65, 113, 777)
+COLSUM_COLS = (1, 63, 64, 65, 130)
