@@ -547,6 +547,20 @@ int mp_lora_grad_unpack_partials_f32(const float* dBp, const float* dATp, int ch
 /* mp_lora_pack for `n` adapters in one launch: descs = n x 104 bytes on the device {const float* a, b; const int64_t* rows; bf16* A, AT, B, BT, Bx;
  * int64 ldbx; int r, fin, fout, k0, W; float bscale, xscale; int pad}, max_elems = the largest r * fin + fout * r among them. */
 int mp_lora_pack_batched(const void* descs, int n, int64_t max_elems, hipStream_t stream);
+/* One adapter merged into the rows of a (fused) projection weight, source and destination apart (peft merge_and_unload,
+ * merge_lora_weights_and_save_hf_model_moe.py:339: W += scaling * B A): for o < fout, c < fin
+ *   Wdst[rows[o] * lddst + c] = bf16(float(Wsrc[rows[o] * ldsrc + c]) + scaling * sum_{j < r} b[o * r + j] * a[j * fin + c])
+ * with the sum started from zero and accumulated in fp32, j ascending (no atomics: the same inputs give the same bits on every launch).
+ * a [r, fin], b [fout, r]: the fp32 master parameters, as mp_lora_pack reads them (any 4-byte alignment); rows: the adapter's output rows
+ * inside the fused matrix (q / k / v thirds, interleaved gate | up).  Rows of Wdst that `rows` does not name are not touched; Wsrc == Wdst is
+ * allowed.  0 < r <= 64, fin % 8 == 0, ldsrc % 8 == 0, lddst % 8 == 0, both >= fin (MP_ERR_SHAPE); null operands with fout > 0: MP_ERR_ARG;
+ * fout == 0: MP_OK, nothing launched.  One pass, every weight read and written once. */
+int mp_lora_merge_rows_bf16(const void* Wsrc, int64_t ldsrc, void* Wdst, int64_t lddst, const float* a, const float* b, const int64_t* rows,
+                            int r, int fin, int fout, float scaling, hipStream_t stream);
+/* mp_lora_merge_rows_bf16 for `n` adapters in one launch: descs = n x 72 bytes on the device {const bf16* Wsrc; bf16* Wdst; const float* a, b;
+ * const int64_t* rows; int64 ldsrc, lddst; int r, fin, fout; float scaling}.  An entry that breaks the shape rules above is skipped (the
+ * host does not see the table).  n == 0: MP_OK, nothing launched. */
+int mp_lora_merge_rows_batched(const void* descs, int n, hipStream_t stream);
 /* Backward of the adapter branch into the projection's input gradient in one pass: out = dx + dropout(bf16(dt A)) with the forward's mask
  * (dt [tokens, >= R] = scaling * dY B, AT [K, 64] = A^T padded: mp_lora_pack; p = 0: no mask).  Replaces a thin GEMM, mp_dropout_bf16 and
  * mp_add3_bf16 with the same rounding points.  R in {8, 16, 32}; out may alias dx. */

@@ -100,6 +100,8 @@ class LoRAState(torch.nn.Module):
         self.ext = {}                                           # (layer, group) -> extended weight [out, in + 64] (enable_lora)
         self.p_active = self.p                                  # dropout in effect: p while training, 0 in eval (set per forward)
         self.keep_bits = {}                                     # seed -> lora_dropout mask bytes the forward left for the same step's backward
+        self.shadow_live = False                                # merge_shadow() wrote lw[k] = bf16(W + scaling B A); restore_plain() clears it
+        self.shadow_epoch = None                                # ops.PARAM_EPOCH the live shadow was built at
         self.wgrad_stream = None                                # MP_LORA_WGRAD_STREAM=1: where dA^T = drop(x)^T dt and the gradient unpack run (off the dgrad chain)
 
     def _modules_of(self, i, t):
@@ -222,6 +224,8 @@ class LoRAState(torch.nn.Module):
     def merge_into(self, llm):
         """peft merge_and_unload (merge_lora_weights_and_save_hf_model_moe.py:339): W += scaling * B A for every adapter, into the
         model's bf16 weights in place (the fused / interleaved / per-expert row layouts included); fully fine-tuned matrices are synced."""
+        if self.shadow_live:                                      # start from the pristine weights, not from a shadow of them
+            self.restore_plain(llm)
         self.sync_model(llm)
         for i, lw in enumerate(llm.layers):
             for t in self.targets:
@@ -240,6 +244,55 @@ class LoRAState(torch.nn.Module):
                 if k + "_x" in lw:
                     lw[k + "_x"][..., :lw[k].shape[-1]].copy_(lw[k])
         llm.refresh_fused_qkv()                                   # the RoPE-interleaved copies follow the merged q / k / v weights
+
+    def _shadow_groups(self, llm):
+        """(layer weights, group) of every adapted group; each has its pristine copy in the first K columns of lw[group + "_x"]."""
+        if llm.ep is not None:
+            raise RuntimeError("a shadow merge needs the pristine copy of every adapted weight ([W | scaling B], enable_lora); under expert "
+                               "parallelism the sharded experts keep none: merge_and_unload() first")
+        adapted = [g for g, mem in GROUPS.items() if any(t in self.targets for t in mem)]
+        return [(lw, g) for lw in llm.layers for g in adapted]
+
+    @torch.no_grad()
+    def merge_shadow(self, llm):
+        """Non-destructive merge for decoding with the adapters attached: lw[k] = bf16(W + scaling * B A) for every adapted group, W read from
+        the pristine copy in lw[k + "_x"][..., :K] (which the training forward and backward keep using, with lw[k + "_T"]), all adapters in one
+        launch of mp_lora_merge_rows_batched.  What the decode paths then compute is what merge_and_unload() would ship (the reference
+        merges before inference: merge_lora_weights_and_save_hf_model_moe.py:339).  restore_plain() undoes it bit for bit."""
+        groups = self._shadow_groups(llm)
+        self.sync_model(llm)                                      # trained lm_head / embed_tokens / norms / gate / projector are the current ones
+        items = []
+        for i, lw in enumerate(llm.layers):
+            for t in self.targets:
+                grp = next(g for g, mem in GROUPS.items() if t in mem)
+                K = lw[grp].shape[-1]
+                for e, _ in enumerate(self._modules_of(i, t)):
+                    src, dst = (lw[grp + "_x"], lw[grp]) if lw[grp].dim() == 2 else (lw[grp + "_x"][e], lw[grp][e])
+                    items.append((src[:, :K], dst, self.get(i, t, "A", e).detach(), self.get(i, t, "B", e).detach(), self.rows[t], self.scaling))
+        key = tuple((x[0].data_ptr(), x[1].data_ptr(), x[2].data_ptr(), x[3].data_ptr()) for x in items)
+        if getattr(self, "_shadow_key", None) != key:             # (the engine re-homes the parameters into its flat buffer once)
+            self._shadow_tab, self._shadow_n = ops.lora_merge_table(items, self.rows["q_proj"].device)
+            self._shadow_key = key
+        self.shadow_live = True
+        ops.lora_merge_rows_batched(self._shadow_tab, self._shadow_n)
+        self._refresh_derived(llm)
+        self.shadow_epoch = ops.PARAM_EPOCH
+        return len(groups)
+
+    @torch.no_grad()
+    def restore_plain(self, llm):
+        """Undo merge_shadow: every adapted lw[k] copied back from its pristine copy, the RoPE-interleaved (and norm-folded) images rebuilt."""
+        for lw, g in self._shadow_groups(llm):
+            lw[g].copy_(lw[g + "_x"][..., :lw[g].shape[-1]])
+        self._refresh_derived(llm)
+        self.shadow_live = False
+
+    def _refresh_derived(self, llm):
+        """The weight images the multi-row forward derives from lw["qkv"] / lw["gu"] (llama.refresh_fused_qkv / refresh_folded_norms)."""
+        if llm.fuse_rope and any(t in GROUPS["qkv"] for t in self.targets):
+            llm.refresh_fused_qkv()
+        elif any("gu_f" in lw for lw in llm.layers) and any(t in GROUPS["gu"] for t in self.targets):
+            llm.refresh_folded_norms()
 
     def padded(self, i):
         """bf16 GEMM operands of layer i per adapter group: (A [64, in], A^T [in, 64], B [out, 64], B^T [64, out], R, targets) — with a

@@ -9,6 +9,7 @@ per-sample splice loop, per-mask decoder loop) is replaced by batched kernels.
 Dead work the reference performs but never consumes is not executed (results are identical — row-wise ops):
 full-vocabulary fp32 logits for unsupervised rows, text_hidden_fcs on non-<SEG> rows, the 32 intermediate hidden
 states, CLIP's last layer, mask tokens 1-3."""
+import contextlib
 import math
 import os
 from typing import List, Optional
@@ -192,6 +193,7 @@ class MedPLIBForCausalLM(nn.Module):
         # against the next tail by the tail stream itself.  Anything else that touches trainable state calls sync_side_streams().
         self.decode_with_graph = True            # evaluate(): replay one captured HIP graph per generated token
         self.last_decode_path = None             # "graph" or "loop": how the last generate() / evaluate() decoded
+        self._shadow_depth = 0                   # open adapters_merged() blocks (the decode entry points nest inside a caller's)
         self.tail_side_stream = False
         self._tail_stream_obj = None
         self.active_tail_stream = None
@@ -277,9 +279,44 @@ class MedPLIBForCausalLM(nn.Module):
             raise RuntimeError(f"{what}() works on the plain weights (KV-cache decode, export): call merge_and_unload() first (the "
                                "reference merges its adapters before inference too, merge_lora_weights_and_save_hf_model_moe.py)")
 
+    @contextlib.contextmanager
+    def adapters_merged(self):
+        """Decode with the adapters attached, like a peft model: inside the block the plain weights the KV-cache decode paths read hold
+        bf16(W + scaling * B A) (LoRAState.merge_shadow: one launch, the pristine weights stay in their [W | scaling B] copies, which is all
+        the training forward and backward read); leaving it, also on an exception, puts them back bit for bit.  Re-entrant: evaluate() /
+        generate() / generate_stream() open it themselves, inside a caller's block they reuse its shadow and rebuild it only when the
+        parameters were written since (ops.PARAM_EPOCH: an optimizer step, a checkpoint load).  Without adapters: nothing happens."""
+        lora = getattr(self.model, "lora", None)
+        if lora is None:
+            yield self
+            return
+        llm = self.model.llm
+        self._require_shadowable("adapters_merged")
+        self._shadow_depth += 1
+        try:
+            if self._shadow_depth == 1 or lora.shadow_epoch != ops.PARAM_EPOCH:
+                self.sync_side_streams()
+                lora.merge_shadow(llm)
+            yield self
+        finally:
+            self._shadow_depth -= 1
+            if self._shadow_depth == 0:
+                lora.restore_plain(llm)
+
+    def _require_shadowable(self, what):
+        """Adapters attached under expert parallelism cannot decode: checked by the decode entry points before they change any state."""
+        if getattr(self.model, "lora", None) is not None and self.model.llm.ep is not None:
+            raise RuntimeError(f"{what}() with adapters attached is not built for expert parallelism (the sharded experts keep no pristine copy "
+                               "of their weights to restore from): call merge_and_unload() first")
+
+    def _refuse_in_shadow(self, what):
+        if self._shadow_depth > 0:
+            raise RuntimeError(f"{what}() inside an open adapters_merged() block: the plain weights hold the shadow merge; leave the block first")
+
     def merge_and_unload(self):
         """peft `merge_and_unload()`: fold the trained adapters into the weights and drop them; inference / evaluate() / export then see
         the fine-tuned model (the adapters only act in the training forward)."""
+        self._refuse_in_shadow("merge_and_unload")
         if getattr(self.model, "lora", None) is not None:
             self.model.lora.merge_into(self.model.llm)
             self.model.lora = None
@@ -352,6 +389,7 @@ class MedPLIBForCausalLM(nn.Module):
         fields -- the hand-over to the reference's inference scripts after training / merging here."""
         import dataclasses
         import json
+        self._refuse_in_shadow("save_pretrained")
         os.makedirs(save_path, exist_ok=True)
         sd = state_dict if state_dict is not None else self.hf_state_dict()
         torch.save({k: v.detach().cpu() for k, v in sd.items()}, os.path.join(save_path, "pytorch_model.bin"))
@@ -623,7 +661,7 @@ class MedPLIBForCausalLM(nn.Module):
                 m.llm.lora.sync_model(m.llm)                        # bf16 working copies of lm_head / embed_tokens when they train
             embeds = ops.splice_rows(m.llm.embed_tokens, feats, src, cfg.hidden_size).view(B, plan.seq_len, cfg.hidden_size)
             # adapters attached: they act in every forward of this method (training, validation, inference masks) like a peft
-            # model; the KV-cache decode paths want them merged (merge_and_unload())
+            # model; the KV-cache decode paths run on their shadow merge (adapters_merged())
             lora_train = m.llm.lora is not None
             if not lora_train:
                 last_hidden, aux, self._routing = m.llm.forward(embeds, key_valid, collect_routing=self.capture_intermediates)
@@ -891,26 +929,27 @@ class MedPLIBForCausalLM(nn.Module):
                                  "return_dict_in_generate", "pad_token_id"}
         if unknown:
             raise TypeError(f"generate(): unsupported arguments {sorted(unknown)}")
+        self._require_shadowable("generate")
         self.sync_side_streams()
-        self._require_merged("generate")
         ids = _np_ids(input_ids).astype(np.int64)
         was_training = self.training
         self.train(False)
         rows = []
-        for b in range(ids.shape[0]):
-            row = ids[b:b + 1]
-            if attention_mask is not None:
-                row = row[:, _np_ids(attention_mask)[b].astype(bool)]               # drop this row's padding
-            img = images[b] if isinstance(images, (list, tuple)) else images[b:b + 1]
-            if isinstance(images, (list, tuple)):
-                img = [img]
-            rm, rv = kwargs.get("region_masks") or (), kwargs.get("valid_region_masks_bool") or ()
-            if len(rm) > 0:            # the collator's flat list holds one entry per sample WITH regions: pick this row's
-                before = sum(1 for v in rv[:b] if any(v))
-                rm, rv = (rm[before:before + 1] if any(rv[b]) else ()), rv[b:b + 1]
-            out, _ = self._greedy(row, img, max_new_tokens, eos_token_id, kwargs.get("mask_images"), kwargs.get("image_token_types"),
-                                  kwargs.get("image_token_lengths"), rm, rv)
-            rows.append(out[0])
+        with self.adapters_merged():                 # adapters attached: decode on their shadow merge, restored on the way out
+            for b in range(ids.shape[0]):
+                row = ids[b:b + 1]
+                if attention_mask is not None:
+                    row = row[:, _np_ids(attention_mask)[b].astype(bool)]               # drop this row's padding
+                img = images[b] if isinstance(images, (list, tuple)) else images[b:b + 1]
+                if isinstance(images, (list, tuple)):
+                    img = [img]
+                rm, rv = kwargs.get("region_masks") or (), kwargs.get("valid_region_masks_bool") or ()
+                if len(rm) > 0:            # the collator's flat list holds one entry per sample WITH regions: pick this row's
+                    before = sum(1 for v in rv[:b] if any(v))
+                    rm, rv = (rm[before:before + 1] if any(rv[b]) else ()), rv[b:b + 1]
+                out, _ = self._greedy(row, img, max_new_tokens, eos_token_id, kwargs.get("mask_images"), kwargs.get("image_token_types"),
+                                      kwargs.get("image_token_lengths"), rm, rv)
+                rows.append(out[0])
         self.train(was_training)
         n = max(r.shape[0] for r in rows)
         return torch.from_numpy(np.stack([np.concatenate([r, np.full(n - r.shape[0], eos_token_id, np.int64)]) for r in rows]))
@@ -936,8 +975,8 @@ class MedPLIBForCausalLM(nn.Module):
         there only when `images` (the SAM input, with resize_list and original_size_list as in evaluate()) was given and a generated id
         is seg_token_idx: evaluate()'s mask of the first <SEG>.
         debug: a list that receives (fp32 logits row on the host, u or None, token) for every kept token (tests; costs a sync per token)."""
+        self._require_shadowable("generate_stream")
         self.sync_side_streams()
-        self._require_merged("generate_stream")
         ids = _np_ids(input_ids).astype(np.int64)
         assert ids.shape[0] == 1, "generate_stream() decodes one sample, like the reference's worker"
         if attention_mask is not None:
@@ -949,6 +988,8 @@ class MedPLIBForCausalLM(nn.Module):
         due = lambda i: i % every == 0 or i == max_new_tokens - 1            # noqa: E731  the reference's condition on the token number
         looks = [i + 1 for i in range(max_new_tokens) if due(i)]
         was_training = self.training
+        shadow = contextlib.ExitStack()
+        shadow.enter_context(self.adapters_merged())         # adapters attached: their shadow merge lives as long as this generator
         self.train(False)
         steps = self._decode(ids, images_clip, max_new_tokens, stop_ids, region_masks=region_masks, valid_region_masks_bool=valid_region_masks_bool,
                              pick=pick, looks=looks, host_pick=uniforms is not None, debug=debug)
@@ -970,6 +1011,7 @@ class MedPLIBForCausalLM(nn.Module):
         finally:
             steps.close()
             self.train(was_training)
+            shadow.close()
 
     def _seg_mask(self, output_ids, hiddens, images, resize_list, original_size_list, image_token_lengths=None):
         """The mask of one decoded sample (MedPLIB.py:608-680): the hidden state that predicts the first <SEG> of output_ids (position -2
@@ -1013,14 +1055,15 @@ class MedPLIBForCausalLM(nn.Module):
         tokens (the last generated token is never fed back), i.e. one position FEWER than build_seg_token_mask(output_ids)
         yields; the mask's final position is always False (shifted mask), so it is truncated to the hidden length."""
         cfg, dev, m = self.config, self.device_, self.model
+        self._require_shadowable("evaluate")
         self.sync_side_streams()
-        self._require_merged("evaluate")
         ids = _np_ids(input_ids).astype(np.int64)
         assert ids.shape[0] == 1, "evaluate() decodes one sample at a time, like the reference's validate_seg (vqa_infer.py:528)"
         was_training = self.training
         self.train(False)
-        output_ids, hiddens = self._greedy(ids, images_clip, max_new_tokens, eos_token_id, mask_images, image_token_types, image_token_lengths,
-                                           region_masks, valid_region_masks_bool)
+        with self.adapters_merged():                 # adapters attached: decode on their shadow merge, restored on the way out
+            output_ids, hiddens = self._greedy(ids, images_clip, max_new_tokens, eos_token_id, mask_images, image_token_types, image_token_lengths,
+                                               region_masks, valid_region_masks_bool)
         if (output_ids[:, 1:] == self.seg_token_idx).sum() == 0 and inference_demo:
             self.train(was_training)
             return torch.from_numpy(output_ids), []

@@ -595,6 +595,53 @@ def lora_pack(a, b, rows, A, AT, B, BT, k0, bscale=1.0, Bx=None, xscale=1.0):
                _p(Bx), Bx.stride(0) if Bx is not None else 0, float(xscale), _stream())
 
 
+def _merge_operands(w_src, w_dst, a, b, rows):
+    """The checks lora_merge_rows and lora_merge_table share -> (r, fin, fout)."""
+    _chk(w_src, torch.bfloat16, "lora_merge_rows.w_src"); _chk(w_dst, torch.bfloat16, "lora_merge_rows.w_dst")
+    _chk(a, torch.float32, "lora_merge_rows.a"); _chk(b, torch.float32, "lora_merge_rows.b"); _chk(rows, torch.int64, "lora_merge_rows.rows")
+    r, fin = a.shape
+    fout = b.shape[0]
+    assert b.shape[1] == r and rows.numel() == fout and a.is_contiguous() and b.is_contiguous() and rows.is_contiguous()
+    assert w_src.dim() == 2 and w_dst.dim() == 2 and w_src.shape == w_dst.shape and w_src.shape[1] == fin and fout <= w_dst.shape[0], \
+        "lora_merge_rows: w_src / w_dst are [W >= fout, fin] views of the same shape"
+    assert w_src.stride(1) == 1 and w_dst.stride(1) == 1 and w_src.stride(0) >= fin and w_dst.stride(0) >= fin
+    return r, fin, fout
+
+
+def lora_merge_rows(w_src, w_dst, a, b, rows, scaling):
+    """w_dst[rows] = bf16(w_src[rows].float() + scaling * (b @ a)) in one pass (mp_lora_merge_rows_bf16): fp32 masters a [r, fin], b [fout, r];
+    w_src / w_dst bf16 [W, fin] views (any row stride that is a multiple of 8, the same tensor allowed); other rows of w_dst stay."""
+    r, fin, fout = _merge_operands(w_src, w_dst, a, b, rows)
+    lib().call("mp_lora_merge_rows_bf16", _p(w_src), w_src.stride(0), _p(w_dst), w_dst.stride(0), _p(a), _p(b), _p(rows), r, fin, fout,
+               float(scaling), _stream())
+    return w_dst
+
+
+def lora_merge_table(items, device):
+    """The device descriptor table of mp_lora_merge_rows_batched for items = [(w_src, w_dst, a, b, rows, scaling)] -> (uint8 table, n).  The
+    table holds raw pointers: the caller keeps the tensors alive and rebuilds it when one of them moves."""
+    import numpy as np
+    desc = np.dtype([("src", "<u8"), ("dst", "<u8"), ("a", "<u8"), ("b", "<u8"), ("rows", "<u8"), ("ldsrc", "<i8"), ("lddst", "<i8"),
+                     ("r", "<i4"), ("fin", "<i4"), ("fout", "<i4"), ("scaling", "<f4")])
+    assert desc.itemsize == 72
+    recs = []
+    for w_src, w_dst, a, b, rows, scaling in items:
+        r, fin, fout = _merge_operands(w_src, w_dst, a, b, rows)
+        assert 0 < r <= 64 and fin % 8 == 0 and w_src.stride(0) % 8 == 0 and w_dst.stride(0) % 8 == 0 and w_src.data_ptr() % 16 == 0 \
+            and w_dst.data_ptr() % 16 == 0, "lora_merge_table: 0 < r <= 64, fin and the row strides multiples of 8"
+        recs.append((w_src.data_ptr(), w_dst.data_ptr(), a.data_ptr(), b.data_ptr(), rows.data_ptr(), w_src.stride(0), w_dst.stride(0), r, fin, fout,
+                     float(scaling)))
+    arr = np.array(recs, dtype=desc)
+    return torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to(device), len(recs)
+
+
+def lora_merge_rows_batched(table, n):
+    """Every adapter of a lora_merge_table in one launch (mp_lora_merge_rows_batched)."""
+    _chk(table, torch.uint8, "lora_merge_rows_batched.table")
+    assert table.numel() == 72 * n
+    lib().call("mp_lora_merge_rows_batched", _p(table), int(n), _stream())
+
+
 def lora_grad_unpack(dB, dAT, rows, k0, gB, gA):
     """gB [fout, r] += dB[rows, k0:k0 + r], gA [r, fin] += dAT[:, k0:k0 + r].T in one launch (mp_lora_grad_unpack_f32); all fp32, contiguous."""
     for t_, n_ in ((dB, "dB"), (dAT, "dAT"), (gB, "gB"), (gA, "gA")):
