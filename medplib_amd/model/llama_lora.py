@@ -12,10 +12,12 @@ N-tile; gate and up share one pair on the fused, interleaved gate|up matrix).  T
 with −sin, adapter weight gradients by `mp_tn_skinny_f32` (fixed summation order: the step stays bit-reproducible).
 autograd sees three Functions: LlamaLoRAFn (the stack), CrossEntropyFn (lm_head + filtered CE), GatherRowsFn (<SEG> rows for the
 fp32 tail); everything inside them is this library's kernels.  Targets: any of q/k/v/o/gate/up/down_proj (the shipped scripts' sets).
-MoE layers (top-1, one rank): per-expert adapters on the capacity slabs, the routed dgrad, the gate-probability and l_aux gradients
-into the gate and a trainable `wg` (scripts/train_stage4.sh's `--sft_modules wg,...`)."""
+MoE layers (top-1 and top-2 on one rank; top-1 with the experts sharded over an expert-parallel group): per-expert adapters on the
+capacity slabs, the routed dgrad, the gate-probability and l_aux gradients into the gate and a trainable `wg` (scripts/train_stage4.sh's
+`--sft_modules wg,...`)."""
 import math
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -41,6 +43,23 @@ def decoder_param_names(lora):
 
 def _module(t):
     return ("self_attn." if t in ("q_proj", "k_proj", "v_proj", "o_proj") else "mlp.") + t
+
+
+class AdapterOps(NamedTuple):
+    """bf16 GEMM operands of one adapter group (LoRAState.padded) — with a leading expert axis for the MLP groups of a MoE layer, and B stored
+    * scaling there (the batched GEMM has no alpha)."""
+    A: torch.Tensor        # [64, in]
+    AT: torch.Tensor       # [in, 64]
+    B: torch.Tensor        # [out, 64]
+    BT: torch.Tensor       # [64, out]
+    R: int                 # rank of the fused pair (targets x r), rounded up to what the wgrad kernel takes
+    targets: tuple         # the group's targets that carry adapters, in GROUPS order: target k owns columns k * r .. of the pair
+
+
+class AdapterIn(NamedTuple):
+    """What the forward keeps per adapter group (s["adapter_in"][group], dense and MoE layers alike) for the group's backward."""
+    x: torch.Tensor        # the adapter's input, undropped (the two-GEMM MoE form keeps the dropped copy it made: it has no mask to regenerate)
+    t: torch.Tensor        # bf16(dropout(x) A^T): the extension columns of the projection's input ([.., 64])
 
 
 class LoRAState(torch.nn.Module):
@@ -96,12 +115,18 @@ class LoRAState(torch.nn.Module):
         # set by the engine for data-parallel runs: callable(layer, {name: gradient}) invoked by backward() as soon as a layer's
         # gradients are complete, so their all-reduce overlaps the dgrad of the layers below (engine.Engine._sink)
         self.grad_sink = None
-        self._bufs = {}
+        self._bufs = {}                                         # layer -> {group: AdapterOps}, persistent (padded)
+        self._packed_at = self._packed_epoch = None             # lora.step / ops.PARAM_EPOCH at which pack_all() last rewrote every slice
+        self._pack_key = self._pack_tab = None                  # pack_all's descriptor table and the pointers it was built for
+        self._pack_max = 0
+        self.sink_reduces = True                                # whether the sink starts a collective on a layer's gradients (engine.Engine sets it): False = nothing reads them before backward() ends
         self.ext = {}                                           # (layer, group) -> extended weight [out, in + 64] (enable_lora)
         self.p_active = self.p                                  # dropout in effect: p while training, 0 in eval (set per forward)
         self.keep_bits = {}                                     # seed -> lora_dropout mask bytes the forward left for the same step's backward
         self.shadow_live = False                                # merge_shadow() wrote lw[k] = bf16(W + scaling B A); restore_plain() clears it
         self.shadow_epoch = None                                # ops.PARAM_EPOCH the live shadow was built at
+        self._shadow_key = self._shadow_tab = None              # merge_shadow's descriptor table and the pointers it was built for
+        self._shadow_n = 0
         self.wgrad_stream = None                                # MP_LORA_WGRAD_STREAM=1: where dA^T = drop(x)^T dt and the gradient unpack run (off the dgrad chain)
 
     def _modules_of(self, i, t):
@@ -113,25 +138,26 @@ class LoRAState(torch.nn.Module):
         mod = self._modules_of(i, t)[e if e is not None else 0]
         return self.params[self.index[f"model.layers.{i}.{mod}.lora_{which}.default.weight"]]
 
+    def _add_masters(self, items):
+        """fp32 master parameters of front-end tensors that train whole: [(name, the module's working tensor)]."""
+        for n, t in items:
+            self.index[n] = len(self.names)
+            self.names.append(n)
+            self.params.append(torch.nn.Parameter(t.detach().float().clone()))
+
     def add_projector(self, tower):
         """`mm_projector` in --sft_modules (train_stage2.sh): the two Linears train whole; fp32 masters here, bf16 working copies
         (and W2^T for the dgrad) in the tower."""
         self.tower = tower
         pr = tower.proj
-        for n, t in (("model.mm_projector.0.weight", pr["w0"]), ("model.mm_projector.0.bias", pr["b0"]),
-                     ("model.mm_projector.2.weight", pr["w2"]), ("model.mm_projector.2.bias", pr["b2"])):
-            self.index[n] = len(self.names)
-            self.names.append(n)
-            self.params.append(torch.nn.Parameter(t.detach().float().clone()))
+        self._add_masters((("model.mm_projector.0.weight", pr["w0"]), ("model.mm_projector.0.bias", pr["b0"]),
+                           ("model.mm_projector.2.weight", pr["w2"]), ("model.mm_projector.2.bias", pr["b2"])))
         pr["w2_T"] = pr["w2"].t().contiguous()
 
     def add_region_adapter(self, tower):
         """`region_fea_adapter` in --sft_modules (scripts/train_stage4.sh:33): the Linear on the raw tower features trains whole."""
         self.region_tower = tower
-        for n, t in (("model.region_fea_adapter.weight", tower.region_adapter["w"]), ("model.region_fea_adapter.bias", tower.region_adapter["b"])):
-            self.index[n] = len(self.names)
-            self.names.append(n)
-            self.params.append(torch.nn.Parameter(t.detach().float().clone()))
+        self._add_masters((("model.region_fea_adapter.weight", tower.region_adapter["w"]), ("model.region_fea_adapter.bias", tower.region_adapter["b"])))
 
     def add_mask_encoder(self, enc):
         """`mask_encoder` in --sft_modules (scripts/train_medplib_icl.sh:12): the four convolutions, the projection and the LayerNorm of
@@ -142,19 +168,13 @@ class LoRAState(torch.nn.Module):
             items += [(f"model.mask_encoder.encoder.{i}.weight", enc.convs[j][0]), (f"model.mask_encoder.encoder.{i}.bias", enc.convs[j][1])]
         items += [("model.mask_encoder.proj.weight", enc.proj_w), ("model.mask_encoder.proj.bias", enc.proj_b),
                   ("model.mask_encoder.norm.weight", enc.norm[0]), ("model.mask_encoder.norm.bias", enc.norm[1])]
-        for n, t in items:
-            self.index[n] = len(self.names)
-            self.names.append(n)
-            self.params.append(torch.nn.Parameter(t.detach().float().clone()))
+        self._add_masters(items)
 
     def add_token_compressor(self, comp):
         """`mm_token_compressor` in --sft_modules (scripts/train_medplib_icl.sh:8): LayerNorm + Linear train; fp32 masters here."""
         self.comp = comp
-        for n, t in (("model.mm_token_compressor.norm.weight", comp.norm[0]), ("model.mm_token_compressor.norm.bias", comp.norm[1]),
-                     ("model.mm_token_compressor.proj.weight", comp.proj_w), ("model.mm_token_compressor.proj.bias", comp.proj_b)):
-            self.index[n] = len(self.names)
-            self.names.append(n)
-            self.params.append(torch.nn.Parameter(t.detach().float().clone()))
+        self._add_masters((("model.mm_token_compressor.norm.weight", comp.norm[0]), ("model.mm_token_compressor.norm.bias", comp.norm[1]),
+                           ("model.mm_token_compressor.proj.weight", comp.proj_w), ("model.mm_token_compressor.proj.bias", comp.proj_b)))
         comp.proj_w_T = comp.proj_w.t().contiguous()
 
     def full_param(self, name):
@@ -270,7 +290,7 @@ class LoRAState(torch.nn.Module):
                     src, dst = (lw[grp + "_x"], lw[grp]) if lw[grp].dim() == 2 else (lw[grp + "_x"][e], lw[grp][e])
                     items.append((src[:, :K], dst, self.get(i, t, "A", e).detach(), self.get(i, t, "B", e).detach(), self.rows[t], self.scaling))
         key = tuple((x[0].data_ptr(), x[1].data_ptr(), x[2].data_ptr(), x[3].data_ptr()) for x in items)
-        if getattr(self, "_shadow_key", None) != key:             # (the engine re-homes the parameters into its flat buffer once)
+        if self._shadow_key != key:             # (the engine re-homes the parameters into its flat buffer once)
             self._shadow_tab, self._shadow_n = ops.lora_merge_table(items, self.rows["q_proj"].device)
             self._shadow_key = key
         self.shadow_live = True
@@ -295,43 +315,39 @@ class LoRAState(torch.nn.Module):
             llm.refresh_folded_norms()
 
     def padded(self, i):
-        """bf16 GEMM operands of layer i per adapter group: (A [64, in], A^T [in, 64], B [out, 64], B^T [64, out], R, targets) — with a
-        leading expert axis for the MLP groups of a MoE layer, and B stored * scaling there (the batched GEMM has no alpha).  The
-        buffers persist (zeroed once: the padding never changes); each step one pack kernel per adapter rewrites its slices.
-        R = rank of the fused pair (targets x r), rounded up to what the wgrad kernel takes."""
+        """bf16 GEMM operands of layer i: {group: AdapterOps}.  The buffers persist (zeroed once: the padding never changes); each step one
+        pack kernel per adapter rewrites its slices."""
         r, dev, bf = self.r, self.rows["q_proj"].device, torch.bfloat16
-        moe = i in self.moe_layers
         if i not in self._bufs:
             self._bufs[i] = {}
             for grp, members in GROUPS.items():
-                tg = [t for t in members if t in self.targets]
+                tg = tuple(t for t in members if t in self.targets)
                 if tg:
-                    fin, W = self.get(i, tg[0], "A").shape[1], self.width[grp]
-                    lead = (self.E,) if (moe and grp in ("gu", "down")) else ()
-                    self._bufs[i][grp] = (torch.zeros(lead + (64, fin), dtype=bf, device=dev), torch.zeros(lead + (fin, 64), dtype=bf, device=dev),
-                                          torch.zeros(lead + (W, 64), dtype=bf, device=dev), torch.zeros(lead + (64, W), dtype=bf, device=dev), tg)
-        out = {}
+                    fin, W, R = self.get(i, tg[0], "A").shape[1], self.width[grp], len(tg) * r
+                    lead = (self.E,) if (i in self.moe_layers and grp in ("gu", "down")) else ()
+                    self._bufs[i][grp] = AdapterOps(torch.zeros(lead + (64, fin), dtype=bf, device=dev), torch.zeros(lead + (fin, 64), dtype=bf, device=dev),
+                                                    torch.zeros(lead + (W, 64), dtype=bf, device=dev), torch.zeros(lead + (64, W), dtype=bf, device=dev),
+                                                    8 if R <= 8 else 16 if R <= 16 else 32 if R <= 32 else 64, tg)
         # pack_all() already rewrote every slice this step AND nothing has written the parameters since (the optimizer step bumps ops.PARAM_EPOCH;
         # a caller between optimizer.step() and the next forward — a merge, an eval helper — must not get the previous values' images)
-        fresh = getattr(self, "_packed_at", None) == self.step and self.step > 0 and getattr(self, "_packed_epoch", None) == ops.PARAM_EPOCH
-        for grp, (A, AT, B, BT, tg) in self._bufs[i].items():
-            batched = A.dim() == 3
-            for k, t in enumerate(tg):
+        fresh = self._packed_at == self.step and self.step > 0 and self._packed_epoch == ops.PARAM_EPOCH
+        if not fresh:
+            for a, b, t, (A, AT, B, BT), k0, bscale, Bx in self.adapters(i):
+                ops.lora_pack(a, b, self.rows[t], A, AT, B, BT, k0, bscale=bscale, Bx=Bx, xscale=self.scaling)
+        return self._bufs[i]
+
+    def adapters(self, i):
+        """Every adapter of layer i with where it is packed: (a [r, in], b [out, r] fp32, target, its (expert's) slices (A, AT, B, BT) of the
+        group's operands, first column k0, the scale B is stored with, Bx).  Bx: the last 64 columns of the group's extended weight
+        [W | scaling B] (of expert e's, [E, out, in + 64]), which take scaling * B as well; None without one."""
+        for grp, o in self._bufs[i].items():
+            batched = o.A.dim() == 3
+            wx = self.ext.get((i, grp))
+            for k, t in enumerate(o.targets):
                 for e in range(self.E if batched else 1):
-                    if fresh:
-                        continue
-                    a, b = self.get(i, t, "A", e).detach(), self.get(i, t, "B", e).detach()
-                    if batched:
-                        wx = self.ext.get((i, grp))                # [E, out, in + 64]: expert e's scaling * B behind its frozen weight
-                        ops.lora_pack(a, b, self.rows[t], A[e], AT[e], B[e], BT[e], k * r, bscale=self.scaling,
-                                      Bx=None if wx is None else wx[e][:, wx.shape[2] - 64:], xscale=self.scaling)
-                    else:
-                        wx = self.ext.get((i, grp))                # dense group: scaling * B also lands in [W | scaling B]'s last 64 columns
-                        ops.lora_pack(a, b, self.rows[t], A, AT, B, BT, k * r, Bx=None if wx is None else wx[:, wx.shape[1] - 64:],
-                                      xscale=self.scaling)
-            R = len(tg) * r
-            out[grp] = (A, AT, B, BT, 8 if R <= 8 else 16 if R <= 16 else 32 if R <= 32 else 64, tg)
-        return out
+                    bx = None if wx is None else (wx[e] if batched else wx)[:, wx.shape[-1] - 64:]
+                    yield (self.get(i, t, "A", e).detach(), self.get(i, t, "B", e).detach(), t, (o.A[e], o.AT[e], o.B[e], o.BT[e]) if batched else o[:4],
+                           k * self.r, self.scaling if batched else 1.0, bx)
 
 
 _PACK_DESC = np.dtype([("a", "<u8"), ("b", "<u8"), ("rows", "<u8"), ("A", "<u8"), ("AT", "<u8"), ("B", "<u8"), ("BT", "<u8"), ("Bx", "<u8"), ("ldbx", "<i8"),
@@ -347,22 +363,13 @@ def pack_all(lora, n_layers):
         if i not in lora._bufs:
             lora.padded(i)
     recs = []
-    r = lora.r
     for i in range(n_layers):
-        moe = i in lora.moe_layers
-        for grp, (A, AT, B, BT, tg) in lora._bufs[i].items():
-            batched = A.dim() == 3
-            wx = lora.ext.get((i, grp))
-            for k, t in enumerate(tg):
-                for e in range(lora.E if batched else 1):
-                    a, b = lora.get(i, t, "A", e).detach(), lora.get(i, t, "B", e).detach()
-                    Ae, ATe, Be, BTe = (A[e], AT[e], B[e], BT[e]) if batched else (A, AT, B, BT)
-                    bx = None if wx is None else (wx[e][:, wx.shape[2] - 64:] if batched else wx[:, wx.shape[1] - 64:])
-                    recs.append((a.data_ptr(), b.data_ptr(), lora.rows[t].data_ptr(), Ae.data_ptr(), ATe.data_ptr(), Be.data_ptr(), BTe.data_ptr(),
-                                 0 if bx is None else bx.data_ptr(), 0 if bx is None else bx.stride(0), a.shape[0], a.shape[1], b.shape[0], k * r, Be.shape[0],
-                                 lora.scaling if batched else 1.0, lora.scaling, 0))
+        for a, b, t, (A, AT, B, BT), k0, bscale, bx in lora.adapters(i):
+            recs.append((a.data_ptr(), b.data_ptr(), lora.rows[t].data_ptr(), A.data_ptr(), AT.data_ptr(), B.data_ptr(), BT.data_ptr(),
+                         0 if bx is None else bx.data_ptr(), 0 if bx is None else bx.stride(0), a.shape[0], a.shape[1], b.shape[0], k0, B.shape[0],
+                         bscale, lora.scaling, 0))
     key = tuple(recs)
-    if getattr(lora, "_pack_key", None) != key:
+    if lora._pack_key != key:
         arr = np.array(recs, dtype=_PACK_DESC)
         lora._pack_tab = torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to(lora.rows["q_proj"].device)
         lora._pack_key, lora._pack_max = key, max(int(x[9]) * int(x[10]) + int(x[11]) * int(x[9]) for x in recs)
@@ -406,12 +413,6 @@ def enable_lora(llm, cfg, r=8, alpha=16, dropout=0.0, targets=MLP_TARGETS, seed=
     return llm.lora
 
 
-def _ext_rows(T, K, dev):
-    """The row-padded input of an extended projection: (whole [T, K + 64] buffer, its [T, K] activation part, its [T, 64] adapter part)."""
-    buf = torch.empty((T, K + 64), dtype=torch.bfloat16, device=dev)
-    return buf, buf[:, :K], buf[:, K:]
-
-
 _ROPE_IN_ATTN_BWD = os.environ.get("MP_ATTN_BWD_ROPE", "1") != "0"      # A/B: 0 = mp_rope_qk_bf16 over the fused gradient after the attention backward
 _FUSE_SWSK = os.environ.get("MP_LORA_FUSE_SWIGLU_SKINNY", "1") != "0"   # A/B: 0 = d gate|up written by one kernel, read back by the gate|up adapter's products
 _FUSE_NORM_UP = os.environ.get("MP_LORA_FUSE_NORM_UP", "1") != "0"      # A/B: 0 = mp_lora_up_add_bf16, then mp_rmsnorm_bwd_bf16
@@ -425,14 +426,34 @@ _FUSE_UP_SWIGLU = os.environ.get("MP_FUSE_UP_SWIGLU", "1") != "0"      # A/B: 0 
 
 
 def _adapter_down(lora, ops_pad, x, t, seed):
-    """t = bf16(dropout(x) A^T) into the extension columns -> x (the wgrad regenerates the mask from the seed: nothing dropped is stored)."""
-    A, _, _, _, R, _ = ops_pad
+    """t = bf16(dropout(x) A^T) into the extension columns -> AdapterIn(x, t) (the wgrad regenerates the mask from the seed: nothing dropped is stored)."""
     kb = None
     if lora.p_active > 0 and _KEEP_BITS and x.shape[1] % 256 == 0:
         # the mask as bytes (1 / 16 of x): the two backward kernels that need the same mask read it instead of hashing again
         kb = lora.keep_bits[seed] = ops.keep_bits_for(x)
-    ops.lora_down(x, A, t, R, lora.p_active, seed, keep_bits=kb)
-    return x
+    ops.lora_down(x, ops_pad.A, t, ops_pad.R, lora.p_active, seed, keep_bits=kb)
+    return AdapterIn(x, t)
+
+
+class _ProjIn:
+    """The input of dense projection `k` (qkv / o / gu / down) over T rows of K channels.  With adapters on the group the projection is ONE GEMM
+    of the K-extended weight lw[k + "_x"] = [W | scaling B] over [x | t]: `x` is the [T, K] part of that buffer, which the producer of the
+    input writes (out=), and feed() fills the 64 adapter columns behind it.  Without adapters `x` is None (the producer allocates its own
+    output) and the weight is lw[k]."""
+
+    def __init__(self, lw, k, T, K, dev):
+        self.k, self.ext = k, k + "_x" in lw
+        self.w = lw[k + "_x"] if self.ext else lw[k]
+        self.buf = torch.empty((T, K + 64), dtype=torch.bfloat16, device=dev) if self.ext else None       # the row-padded input [x | t]
+        self.x, self.t = (self.buf[:, :K], self.buf[:, K:]) if self.ext else (None, None)
+
+    def feed(self, lora, pad, s, seed, plain):
+        """After the producer ran -> the GEMM's A operand: the extended buffer, its adapter columns written (and saved with the input for the
+        backward), or `plain` (the producer's own output) without adapters."""
+        if not self.ext:
+            return plain
+        s["adapter_in"][self.k] = _adapter_down(lora, pad[self.k], self.x, self.t, seed)
+        return self.buf
 
 
 def _zeros(shape, dev):
@@ -440,30 +461,66 @@ def _zeros(shape, dev):
 
 
 def _adapter_fwd_moe(lora, ops_pad, xbuf, ybuf, kept, seed):
-    """Per-expert adapters on the capacity slabs: ybuf + (dropout(xbuf) A_e^T) (scaling B_e)^T -> (y', x_dropped, t)."""
-    A, _, B, _, _, _ = ops_pad
+    """Per-expert adapters on the capacity slabs: ybuf + (dropout(xbuf) A_e^T) (scaling B_e)^T -> (y', AdapterIn(x_dropped, t))."""
     E, cap, _ = xbuf.shape
     xd = ops.dropout_bf16(xbuf, lora.p_active, seed) if lora.p_active > 0 else xbuf
-    t = ops.gemm_batched(xd, A, _zeros((E, cap, 64), xbuf.device), m_dev=kept)
-    return ops.gemm_batched_res(t, B, ybuf, _zeros(ybuf.shape, xbuf.device), m_dev=kept), xd, t
+    t = ops.gemm_batched(xd, ops_pad.A, _zeros((E, cap, 64), xbuf.device), m_dev=kept)
+    return ops.gemm_batched_res(t, ops_pad.B, ybuf, _zeros(ybuf.shape, xbuf.device), m_dev=kept), AdapterIn(xd, t)
 
 
-def _moe_fwd(llm, lora, i, lw, pad, h2, x_mid, s, seed):
-    """DeepSpeed MoE layer (top-1) in training-with-adapters mode on capacity slabs that are zero where no token sits, so every
-    row of every slab is finite and rows without a token contribute nothing to the weight gradients."""
+class Routing(NamedTuple):
+    """One MoE layer's gate and routing as the forward leaves them for the backward (s["route"])."""
+    h2: torch.Tensor       # [T, d] the gate's input rows
+    wg: torch.Tensor       # the gate's weight (LoRAState.gate_weight)
+    gates: torch.Tensor
+    expert: torch.Tensor
+    slot: torch.Tensor
+    weight: torch.Tensor
+    kept: torch.Tensor     # rows routed to each expert (device-side row counts of the slabs)
+    counts: torch.Tensor   # first choices per expert (l_aux)
+
+
+def _moe_route(llm, lora, i, h2):
+    """The gate and the routing of MoE layer i over this rank's rows -> (Routing, l_aux, capacity)."""
     cfg = llm.cfg
-    T, d = h2.shape
-    E, ff = cfg.num_experts, cfg.intermediate_size
+    T, E = h2.shape[0], cfg.num_experts
     cap = llm.capacity(T)
     wg = lora.gate_weight(i, llm)
-    k = cfg.top_k_experts
     logits, gates = ops.moe_gate(h2, wg)
-    if k == 1:
+    if cfg.top_k_experts == 1:
         expert, slot, weight, kept, counts, l_aux = ops.moe_route_top1(gates, cap, llm._gate_draws(i, T, E, gumbel=False))
     else:
         expert, slot, weight, kept, _, l_aux = ops.moe_route_top2(gates, logits, cap, llm._gate_draws(i, T, E, gumbel=True))
         counts = torch.bincount(expert[:T].long(), minlength=E)    # l_aux is built on the FIRST choices (top2gating's mask1)
-    dev = h2.device
+    return Routing(h2, wg, gates, expert, slot, weight, kept, counts), l_aux, cap
+
+
+def _moe_gate_bwd(llm, lora, i, s, d_buf, d_w, d_aux, grads):
+    """The end of a MoE layer's backward: the slabs' input gradients d_buf go back to their tokens (dropped: 0), the combine weights' gradient d_w
+    and l_aux's go into the gate logits, the gate's input gradient is added, and a trainable `wg` gets its gradient.  -> d_h2 [T, d]."""
+    rt, k, E = s["route"], llm.cfg.top_k_experts, llm.cfg.num_experts
+    T, dev = rt.h2.shape[0], d_buf.device
+    ones = torch.ones(T * k, dtype=torch.float32, device=dev)
+    d_h2 = ops.moe_combine(d_buf, rt.expert, rt.slot, ones, None, s["cap"], top_k=k)
+    dl = ops.moe_gate_bwd(rt.gates, rt.expert, rt.slot, d_w, rt.counts, d_aux, 1.0, top_k=k)
+    ops.moe_gate_dgrad_(dl, rt.wg, d_h2)
+    name = f"model.layers.{i}.mlp.deepspeed_moe.gate.wg.weight"
+    if name in lora.index:
+        dlb = torch.zeros((T, 8), dtype=torch.bfloat16, device=dev)
+        dlb[:, :E] = dl
+        grads[name] = ops.tn_skinny(rt.h2, dlb, 8, 1.0)[:, :E].t()
+    return d_h2
+
+
+def _moe_fwd(llm, lora, i, lw, pad, h2, x_mid, s, seed):
+    """DeepSpeed MoE layer (top-1 / top-2) in training-with-adapters mode on capacity slabs that are zero where no token sits, so every
+    row of every slab is finite and rows without a token contribute nothing to the weight gradients."""
+    cfg = llm.cfg
+    T, d = h2.shape
+    E, ff, k = cfg.num_experts, cfg.intermediate_size, cfg.top_k_experts
+    rt, l_aux, cap = _moe_route(llm, lora, i, h2)
+    expert, slot, kept = rt.expert, rt.slot, rt.kept
+    dev, ain = h2.device, s["adapter_in"]
     empty = lambda *shape: torch.empty(shape, dtype=torch.bfloat16, device=dev)
     if "gu_x" in lw:
         # fused adapter branch on the capacity slabs (as the dense layers, per expert): nothing is zero-filled -- rows beyond an expert's
@@ -472,37 +529,35 @@ def _moe_fwd(llm, lora, i, lw, pad, h2, x_mid, s, seed):
         bufx = empty(E, cap, d + 64)
         buf = ops.moe_dispatch(h2, expert, slot, E, cap, buf=bufx[:, :, :d], top_k=k)
         for e in range(E):
-            ops.lora_down(buf[e], pad["gu"][0][e], bufx[e][:, d:], pad["gu"][4], lora.p_active, seed * 16 + e, rows_dev=kept[e:e + 1])
+            ops.lora_down(buf[e], pad["gu"].A[e], bufx[e][:, d:], pad["gu"].R, lora.p_active, seed * 16 + e, rows_dev=kept[e:e + 1])
         gu = ops.gemm_batched(bufx, lw["gu_x"], empty(E, cap, 2 * ff), m_dev=kept)
-        s["bufd"], s["t_gu"] = buf, bufx[:, :, d:]
+        ain["gu"] = AdapterIn(buf, bufx[:, :, d:])
     else:
         buf = ops.moe_dispatch(h2, expert, slot, E, cap, buf=_zeros((E, cap, d), dev), top_k=k)
         gu = ops.gemm_batched(buf, lw["gu"], _zeros((E, cap, 2 * ff), dev), m_dev=kept)
         if "gu" in pad:
-            gu, s["bufd"], s["t_gu"] = _adapter_fwd_moe(lora, pad["gu"], buf, gu, kept, seed)
+            gu, ain["gu"] = _adapter_fwd_moe(lora, pad["gu"], buf, gu, kept, seed)
     if "down_x" in lw:
         actx = empty(E, cap, ff + 64)
         act = actx[:, :, :ff]
         ops.swiglu_pair_fwd(gu.view(E * cap, 2 * ff), out=actx.view(E * cap, ff + 64)[:, :ff], counts=kept, cap=cap)
         for e in range(E):
-            ops.lora_down(act[e], pad["down"][0][e], actx[e][:, ff:], pad["down"][4], lora.p_active, (seed + 1) * 16 + e, rows_dev=kept[e:e + 1])
+            ops.lora_down(act[e], pad["down"].A[e], actx[e][:, ff:], pad["down"].R, lora.p_active, (seed + 1) * 16 + e, rows_dev=kept[e:e + 1])
         y = ops.gemm_batched(actx, lw["down_x"], empty(E, cap, d), m_dev=kept)
-        s["actd"], s["t_d"] = act, actx[:, :, ff:]
+        ain["down"] = AdapterIn(act, actx[:, :, ff:])
     else:
         act = ops.swiglu_pair_fwd(gu.view(E * cap, 2 * ff)).view(E, cap, ff)
         y = ops.gemm_batched(act, lw["down"], _zeros((E, cap, d), dev), m_dev=kept)
         if "down" in pad:
-            y, s["actd"], s["t_d"] = _adapter_fwd_moe(lora, pad["down"], act, y, kept, seed + 1)
-    s["fused_moe"] = ("gu_x" in lw, "down_x" in lw)
-    s.update(moe=True, h2=h2, gates=gates, expert=expert, slot=slot, weight=weight, kept=kept, counts=counts, gu=gu, y=y, cap=cap, wg=wg)
-    return ops.moe_combine(y, expert, slot, weight, x_mid, cap, top_k=k), l_aux
+            y, ain["down"] = _adapter_fwd_moe(lora, pad["down"], act, y, kept, seed + 1)
+    s.update(moe=True, route=rt, fused_moe=("gu_x" in lw, "down_x" in lw), gu=gu, y=y, cap=cap)
+    return ops.moe_combine(y, expert, slot, rt.weight, x_mid, cap, top_k=k), l_aux
 
 
 def _ep_pad(ops_pad, eg, ep):
     """The padded adapter operands of ONE global expert `eg`, broadcast (stride 0) over the `ep` source-rank slabs it serves."""
-    A, AT, B, BT, R, tg = ops_pad
     x = lambda t: t[eg].unsqueeze(0).expand(ep, -1, -1)
-    return (x(A), x(AT), x(B), x(BT), R, tg)
+    return ops_pad._replace(A=x(ops_pad.A), AT=x(ops_pad.AT), B=x(ops_pad.B), BT=x(ops_pad.BT))
 
 
 def _moe_fwd_ep(llm, lora, i, lw, pad, h2, x_mid, s, seed):
@@ -519,13 +574,10 @@ def _moe_fwd_ep(llm, lora, i, lw, pad, h2, x_mid, s, seed):
                                   "(the reference driver's default) needs ep_size 1, or train with --top_k_experts 1")
     T, d = h2.shape
     E, ff = cfg.num_experts, cfg.intermediate_size
-    cap = llm.capacity(T)
-    wg = lora.gate_weight(i, llm)
-    logits, gates = ops.moe_gate(h2, wg)
-    expert, slot, weight, kept, counts, l_aux = ops.moe_route_top1(gates, cap, llm._gate_draws(i, T, E, gumbel=False))
+    rt, l_aux, cap = _moe_route(llm, lora, i, h2)
     capx = ep.exchange_capacity(cap, key=llm.gate_pass)
-    buf = ops.moe_dispatch(h2, expert, slot, E, capx + 1, buf=_zeros((E, capx + 1, d), h2.device))
-    recv, rcounts = ep.dispatch(buf, kept)                                   # [ep, El, capx + 1, d], [ep, El]
+    buf = ops.moe_dispatch(h2, rt.expert, rt.slot, E, capx + 1, buf=_zeros((E, capx + 1, d), h2.device))
+    recv, rcounts = ep.dispatch(buf, rt.kept)                                # [ep, El, capx + 1, d], [ep, El]
     xin = recv[:, :, :capx].permute(1, 0, 2, 3).contiguous()                 # [El, ep, capx, d]: local expert e's slabs are xin[e]
     rc = rcounts.t().contiguous()                                            # [El, ep]
     ids = ep.local_expert_ids()
@@ -534,157 +586,125 @@ def _moe_fwd_ep(llm, lora, i, lw, pad, h2, x_mid, s, seed):
     for e, eg in enumerate(ids):
         w_gu = lw["gu"][e].unsqueeze(0).expand(ep.ep, -1, -1)               # lw holds this rank's E_local experts only
         w_dn = lw["down"][e].unsqueeze(0).expand(ep.ep, -1, -1)
-        st = {}
+        ain = {}
         gu = ops.gemm_batched(xin[e], w_gu, _zeros((ep.ep, capx, 2 * ff), h2.device), m_dev=rc[e])
         if "gu" in pad:
-            gu, st["bufd"], st["t_gu"] = _adapter_fwd_moe(lora, _ep_pad(pad["gu"], eg, ep.ep), xin[e], gu, rc[e], seed * 16 + eg)
+            gu, ain["gu"] = _adapter_fwd_moe(lora, _ep_pad(pad["gu"], eg, ep.ep), xin[e], gu, rc[e], seed * 16 + eg)
         act = ops.swiglu_pair_fwd(gu.view(ep.ep * capx, 2 * ff)).view(ep.ep, capx, ff)
         y = ops.gemm_batched(act, w_dn, _zeros((ep.ep, capx, d), h2.device), m_dev=rc[e])
         if "down" in pad:
-            y, st["actd"], st["t_d"] = _adapter_fwd_moe(lora, _ep_pad(pad["down"], eg, ep.ep), act, y, rc[e], (seed + 1) * 16 + eg)
+            y, ain["down"] = _adapter_fwd_moe(lora, _ep_pad(pad["down"], eg, ep.ep), act, y, rc[e], (seed + 1) * 16 + eg)
         y_loc[e] = y
-        st.update(gu=gu, x=xin[e])
-        loc.append(st)
+        loc.append({"gu": gu, "adapter_in": ain})                           # per local expert: what the dense keys hold per layer
     y_all = ep.combine(y_loc.permute(1, 0, 2, 3).contiguous())              # [E, capx, d]: every global expert's rows for MY tokens
-    s.update(moe=True, ep=True, h2=h2, gates=gates, expert=expert, slot=slot, weight=weight, kept=kept, counts=counts, y=y_all, cap=capx,
-             wg=wg, loc=loc, rc=rc)
-    return ops.moe_combine(y_all, expert, slot, weight, x_mid, capx, top_k=1), l_aux
+    s.update(moe=True, ep=True, route=rt, y=y_all, cap=capx, loc=loc, rc=rc)
+    return ops.moe_combine(y_all, rt.expert, rt.slot, rt.weight, x_mid, capx, top_k=1), l_aux
 
 
-def _moe_bwd_ep(llm, lora, i, lw, s, dx, d_aux, grads, take_e):
+def _moe_bwd_ep(llm, lora, i, lw, s, dx, d_aux, grads, take):
     """Backward of _moe_fwd_ep: the output-row gradients travel to the experts' ranks (`exchange`), each local expert's dgrad and
     adapter gradients run over its slabs (the adapter gradients of the `ep` slabs are summed: they are ONE expert's parameters), the
     input-row gradients travel back (`combine`), then the gate as in _moe_bwd.  Gradients of non-local experts' adapters do not
     exist on this rank (the engine's SUM all-reduce collects each expert's from its owners)."""
     cfg, ep = llm.cfg, llm.ep
-    E, ff, capx = cfg.num_experts, cfg.intermediate_size, s["cap"]
+    ff, capx = cfg.intermediate_size, s["cap"]
     T, d = dx.shape
-    pad, rc = s["pad"], s["rc"]
-    d_y, d_w = ops.moe_combine_bwd(dx, s["y"], s["expert"], s["slot"], s["weight"], capx, top_k=1)        # [E, capx, d]
+    pad, rc, rt = s["pad"], s["rc"], s["route"]
+    d_y, d_w = ops.moe_combine_bwd(dx, s["y"], rt.expert, rt.slot, rt.weight, capx, top_k=1)              # [E, capx, d]
     dy_loc = ep.exchange(d_y).permute(1, 0, 2, 3).contiguous()                                             # [El, ep, capx, d]
     dbuf_loc = torch.empty_like(dy_loc)
     for e, eg in enumerate(ep.local_expert_ids()):
-        st = s["loc"][e]
+        st, ain = s["loc"][e], s["loc"][e]["adapter_in"]
         dn_T = lw["down_T"][e].unsqueeze(0).expand(ep.ep, -1, -1)
         gu_T = lw["gu_T"][e].unsqueeze(0).expand(ep.ep, -1, -1)
         d_act = ops.gemm_batched(dy_loc[e], dn_T, _zeros((ep.ep, capx, ff), dx.device), m_dev=rc[e])
         if "down" in pad:
-            d_act, dB, dAT = _adapter_bwd_moe(lora, _ep_pad(pad["down"], eg, ep.ep), dy_loc[e], st["actd"], st["t_d"], d_act, rc[e],
-                                              (s["seed"] + 1) * 16 + eg)
-            take_e(i, pad["down"], {eg: sum(dB[1:], dB[0])}, {eg: sum(dAT[1:], dAT[0])})
+            d_act, dB, dAT = _adapter_bwd_moe(lora, _ep_pad(pad["down"], eg, ep.ep), dy_loc[e], ain["down"], d_act, rc[e], (s["seed"] + 1) * 16 + eg)
+            take(i, pad["down"], [(eg, sum(dB[1:], dB[0]), sum(dAT[1:], dAT[0]))])
         d_gu = ops.swiglu_pair_bwd(st["gu"].view(ep.ep * capx, 2 * ff), d_act.view(ep.ep * capx, ff)).view(ep.ep, capx, 2 * ff)
         d_in = ops.gemm_batched(d_gu, gu_T, _zeros((ep.ep, capx, d), dx.device), m_dev=rc[e])
         if "gu" in pad:
-            d_in, dB, dAT = _adapter_bwd_moe(lora, _ep_pad(pad["gu"], eg, ep.ep), d_gu, st["bufd"], st["t_gu"], d_in, rc[e], s["seed"] * 16 + eg)
-            take_e(i, pad["gu"], {eg: sum(dB[1:], dB[0])}, {eg: sum(dAT[1:], dAT[0])})
+            d_in, dB, dAT = _adapter_bwd_moe(lora, _ep_pad(pad["gu"], eg, ep.ep), d_gu, ain["gu"], d_in, rc[e], s["seed"] * 16 + eg)
+            take(i, pad["gu"], [(eg, sum(dB[1:], dB[0]), sum(dAT[1:], dAT[0]))])
         dbuf_loc[e] = d_in
     d_buf = ep.combine(dbuf_loc.permute(1, 0, 2, 3).contiguous())                                          # [E, capx, d]
-    ones = torch.ones(T, dtype=torch.float32, device=dx.device)
-    d_h2 = ops.moe_combine(d_buf, s["expert"], s["slot"], ones, None, capx, top_k=1)
-    dl = ops.moe_gate_bwd(s["gates"], s["expert"], s["slot"], d_w, s["counts"], d_aux, 1.0, top_k=1)
-    ops.moe_gate_dgrad_(dl, s["wg"], d_h2)
-    name = f"model.layers.{i}.mlp.deepspeed_moe.gate.wg.weight"
-    if name in lora.index:
-        dlb = torch.zeros((T, 8), dtype=torch.bfloat16, device=dx.device)
-        dlb[:, :E] = dl
-        grads[name] = ops.tn_skinny(s["h2"], dlb, 8, 1.0)[:, :E].t()
-    return d_h2
+    return _moe_gate_bwd(llm, lora, i, s, d_buf, d_w, d_aux, grads)
 
 
-def _adapter_bwd_moe(lora, ops_pad, dy, xd, t, dx, kept, seed):
-    """Per-expert adapter gradients on the slabs: (dx', [dB_e [out, R]], [dA_e^T [in, R]])."""
-    A, AT, B, BT, R, _ = ops_pad
+def _adapter_bwd_moe(lora, ops_pad, dy, ain, dx, kept, seed):
+    """Per-expert adapter gradients on the slabs (ain.x = the DROPPED slabs of the two-GEMM forward): (dx', [dB_e [out, R]], [dA_e^T [in, R]])."""
+    o, (xd, t) = ops_pad, ain
     E, cap, _ = dy.shape
-    dt = ops.gemm_batched(dy, BT, _zeros((E, cap, 64), dy.device), m_dev=kept)            # scaling rides in the packed B
-    dB = [ops.tn_skinny(dy[e], t[e], R, lora.scaling) for e in range(E)]
-    dAT = [ops.tn_skinny(xd[e], dt[e], R, 1.0) for e in range(E)]
+    dt = ops.gemm_batched(dy, o.BT, _zeros((E, cap, 64), dy.device), m_dev=kept)          # scaling rides in the packed B
+    dB = [ops.tn_skinny(dy[e], t[e], o.R, lora.scaling) for e in range(E)]
+    dAT = [ops.tn_skinny(xd[e], dt[e], o.R, 1.0) for e in range(E)]
     if lora.p_active > 0:
-        dxa = ops.dropout_bf16(ops.gemm_batched(dt, AT, _zeros(dx.shape, dy.device), m_dev=kept), lora.p_active, seed)
+        dxa = ops.dropout_bf16(ops.gemm_batched(dt, o.AT, _zeros(dx.shape, dy.device), m_dev=kept), lora.p_active, seed)
         return ops.add3(dx, dxa), dB, dAT
-    return ops.gemm_batched_res(dt, AT, dx, _zeros(dx.shape, dy.device), m_dev=kept), dB, dAT
+    return ops.gemm_batched_res(dt, o.AT, dx, _zeros(dx.shape, dy.device), m_dev=kept), dB, dAT
 
 
-def _adapter_bwd_moe_fused(lora, ops_pad, dy, x, t, dx, kept, seed):
-    """Per-expert adapter gradients for the fused forward (x = the UNdropped slabs, t = their extension columns): dt = dY (scaling B)
+def _adapter_bwd_moe_fused(lora, ops_pad, dy, ain, dx, kept, seed):
+    """Per-expert adapter gradients for the fused forward (ain.x = the UNdropped slabs, ain.t = their extension columns): dt = dY (scaling B)
     by the down-projection kernel, weight gradients limited to each expert's routed rows, dx += dropout(dt A) in place."""
-    A, AT, B, BT, R, _ = ops_pad
+    o, (x, t) = ops_pad, ain
     E, cap, _ = dy.shape
     dB, dAT = [], []
     for e in range(E):
         cnt = kept[e:e + 1]
-        dt = ops.lora_down(dy[e], BT[e], torch.empty((cap, 64), dtype=torch.bfloat16, device=dy.device), R, rows_dev=cnt)    # scaling rides in the packed B
-        dB.append(ops.tn_skinny(dy[e], t[e], R, lora.scaling, rows_dev=cnt))
-        dAT.append(ops.tn_skinny(x[e], dt, R, 1.0, lora.p_active, seed * 16 + e, rows_dev=cnt))
-        if R <= 32:
-            ops.lora_up_add(dt, AT[e], dx[e], R, lora.p_active, seed * 16 + e, rows_dev=cnt)
+        dt = ops.lora_down(dy[e], o.BT[e], torch.empty((cap, 64), dtype=torch.bfloat16, device=dy.device), o.R, rows_dev=cnt)    # scaling rides in the packed B
+        dB.append(ops.tn_skinny(dy[e], t[e], o.R, lora.scaling, rows_dev=cnt))
+        dAT.append(ops.tn_skinny(x[e], dt, o.R, 1.0, lora.p_active, seed * 16 + e, rows_dev=cnt))
+        if o.R <= 32:
+            ops.lora_up_add(dt, o.AT[e], dx[e], o.R, lora.p_active, seed * 16 + e, rows_dev=cnt)
         else:
-            dxa = ops.gemm(dt, AT[e])
+            dxa = ops.gemm(dt, o.AT[e])
             dx[e].copy_(ops.add3(dx[e].contiguous(), ops.dropout_bf16(dxa, lora.p_active, seed * 16 + e) if lora.p_active > 0 else dxa))
     return dx, dB, dAT
 
 
-def _moe_bwd(llm, lora, i, lw, s, dx, d_aux, grads, take_e):
+def _moe_bwd(llm, lora, i, lw, s, dx, d_aux, grads, take):
     """Backward of _moe_fwd: routed dgrad through the experts (+ their adapters), the combine weights' gradient into the gate
     (softmax probability of the chosen expert) together with l_aux's, the gate's input gradient, and d wg.  -> d_h2 [T, d]."""
     cfg = llm.cfg
-    E, ff, cap = cfg.num_experts, cfg.intermediate_size, s["cap"]
+    E, ff, cap, k = cfg.num_experts, cfg.intermediate_size, s["cap"], cfg.top_k_experts
     T, d = dx.shape
-    pad, kept = s["pad"], s["kept"]
-    k = cfg.top_k_experts
-    d_y, d_w = ops.moe_combine_bwd(dx, s["y"], s["expert"], s["slot"], s["weight"], cap, top_k=k)
-    fused_gu, fused_down = s.get("fused_moe", (False, False))
+    pad, rt, ain = s["pad"], s["route"], s["adapter_in"]
+    kept = rt.kept
+    d_y, d_w = ops.moe_combine_bwd(dx, s["y"], rt.expert, rt.slot, rt.weight, cap, top_k=k)
+    fused_gu, fused_down = s["fused_moe"]
     slab = (lambda *shape: torch.empty(shape, dtype=torch.bfloat16, device=dx.device)) if fused_gu and fused_down else (lambda *shape: _zeros(shape, dx.device))
     d_act = ops.gemm_batched(d_y, lw["down_T"], slab(E, cap, ff), m_dev=kept)
     if "down" in pad:
-        d_act, dB, dAT = (_adapter_bwd_moe_fused if fused_down else _adapter_bwd_moe)(lora, pad["down"], d_y, s["actd"], s["t_d"], d_act, kept, s["seed"] + 1)
-        take_e(i, pad["down"], dB, dAT)
+        d_act, dB, dAT = (_adapter_bwd_moe_fused if fused_down else _adapter_bwd_moe)(lora, pad["down"], d_y, ain["down"], d_act, kept, s["seed"] + 1)
+        take(i, pad["down"], list(zip(range(E), dB, dAT)))
     d_gu = ops.swiglu_pair_bwd(s["gu"].view(E * cap, 2 * ff), d_act.view(E * cap, ff), counts=kept if (fused_gu and fused_down) else None,
                                cap=cap).view(E, cap, 2 * ff)
     d_buf = ops.gemm_batched(d_gu, lw["gu_T"], slab(E, cap, d), m_dev=kept)
     if "gu" in pad:
-        d_buf, dB, dAT = (_adapter_bwd_moe_fused if fused_gu else _adapter_bwd_moe)(lora, pad["gu"], d_gu, s["bufd"], s["t_gu"], d_buf, kept, s["seed"])
-        take_e(i, pad["gu"], dB, dAT)
-    ones = torch.ones(T * k, dtype=torch.float32, device=dx.device)
-    d_h2 = ops.moe_combine(d_buf, s["expert"], s["slot"], ones, None, cap, top_k=k)        # rows back to their tokens (dropped: 0)
-    dl = ops.moe_gate_bwd(s["gates"], s["expert"], s["slot"], d_w, s["counts"], d_aux, 1.0, top_k=k)
-    ops.moe_gate_dgrad_(dl, s["wg"], d_h2)
-    name = f"model.layers.{i}.mlp.deepspeed_moe.gate.wg.weight"
-    if name in lora.index:
-        dlb = torch.zeros((T, 8), dtype=torch.bfloat16, device=dx.device)
-        dlb[:, :E] = dl
-        grads[name] = ops.tn_skinny(s["h2"], dlb, 8, 1.0)[:, :E].t()
-    return d_h2
+        d_buf, dB, dAT = (_adapter_bwd_moe_fused if fused_gu else _adapter_bwd_moe)(lora, pad["gu"], d_gu, ain["gu"], d_buf, kept, s["seed"])
+        take(i, pad["gu"], list(zip(range(E), dB, dAT)))
+    return _moe_gate_bwd(llm, lora, i, s, d_buf, d_w, d_aux, grads)       # rows back to their tokens, the gate, d wg
 
 
-def _dense_mlp_fwd(llm, lora, lw, pad, s, seed, h2, gu_ext, x_mid, rows=None):
+def _dense_mlp_fwd(llm, lora, lw, pad, s, seed, h2, pin, x_mid, rows=None):
     """x_mid + down(silu(gate) * up) of a dense layer with its adapters, leaving in `s` what the backward reads.  h2 [T, d] = the normed rows,
-    gu_ext = (the [T, d + 64] buffer h2 lives in, its adapter part) when gate|up carries adapters.  rows (int64 [n]): the MLP runs on compact
-    copies of those rows only and its result is scattered back into x_mid, which is returned."""
+    pin = the _ProjIn of gate|up they were written into.  rows (int64 [n]): the MLP runs on compact copies of those rows only and its result is
+    scattered back into x_mid, which is returned."""
     d, ff, dev = llm.cfg.hidden_size, llm.cfg.intermediate_size, x_mid.device
-    if rows is not None and gu_ext is not None:
-        h2x, h2_c, t3 = _ext_rows(rows.numel(), d, dev)
-        ops.gather_rows_bf16(h2, rows, out=h2_c)
-        h2, gu_ext = h2_c, (h2x, t3)
-    elif rows is not None:
-        h2 = ops.gather_rows_bf16(h2, rows)
-    actx, act, t4 = _ext_rows(h2.shape[0], ff, dev) if "down_x" in lw else (None, None, None)
-    if gu_ext is not None:
-        s["h2d"], s["t_gu"] = _adapter_down(lora, pad["gu"], h2, gu_ext[1], seed), gu_ext[1]
-        gin, gw = gu_ext[0], lw["gu_x"]
-    else:
-        gin, gw = h2, lw["gu"]
+    if rows is not None:
+        pin = _ProjIn(lw, "gu", rows.numel(), d, dev)
+        h2 = ops.gather_rows_bf16(h2, rows, out=pin.x)
+    pdn = _ProjIn(lw, "down", h2.shape[0], ff, dev)
+    gin = pin.feed(lora, pad, s, seed, h2)
     # gate|up: silu(gate) * up from the GEMM's epilogue, which also stores the gate|up values the backward reads
     if _SWIGLU_KEEP:
-        act, gu = ops.gemm_swiglu_keep(gin, gw, act_out=act)
+        act, gu = ops.gemm_swiglu_keep(gin, pin.w, act_out=pdn.x)
     else:                                                  # A/B: the two-kernel form
-        gu = ops.gemm(gin, gw)
-        act = ops.swiglu_pair_fwd(gu, out=act)
+        gu = ops.gemm(gin, pin.w)
+        act = ops.swiglu_pair_fwd(gu, out=pdn.x)
     res = x_mid if rows is None else ops.gather_rows_bf16(x_mid, rows)
-    if "down_x" in lw:
-        s["actd"], s["t_d"] = _adapter_down(lora, pad["down"], act, t4, seed + 1), t4
-        out = ops.gemm(actx, lw["down_x"], residual=res)
-    else:
-        out = ops.gemm(act, lw["down"], residual=res)
+    out = ops.gemm(pdn.feed(lora, pad, s, seed + 1, act), pdn.w, residual=res)
     s["gu"] = gu
     if rows is None:
         return out
@@ -712,35 +732,22 @@ def forward_train(llm, embeds, key_valid):
         needed = None
     for i, lw in enumerate(llm.layers):
         pad = lora.padded(i)
-        s = {"x": x, "pad": pad}
+        s = {"x": x, "pad": pad, "adapter_in": {}}              # adapter_in: group -> AdapterIn
         seed = (lora.step * 4096 + i) * 4
-        if "qkv_x" in lw:
-            h1x, h1, t1 = _ext_rows(T, d, x.device)
-            ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps, out=h1)
-            s["h1d"], s["t_qkv"] = _adapter_down(lora, pad["qkv"], h1, t1, seed + 2), t1
-            qkv = ops.gemm(h1x, lw["qkv_x"], out=ops.padded_rows(T, 3 * d, x.device))
+        pin = _ProjIn(lw, "qkv", T, d, x.device)
+        h1 = ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps, out=pin.x)
+        if "qkv_rope" in lw and not pin.ext:                    # no adapters on q / k / v: RoPE in the GEMM's epilogue as in the frozen forward
+            qkv = ops.gemm_qkv_rope(h1, lw["qkv_rope"], llm.cos, llm.sin, S, H, D, out=ops.padded_rows(T, 3 * d, x.device))
+        else:
+            qkv = ops.gemm(pin.feed(lora, pad, s, seed + 2, h1), pin.w, out=ops.padded_rows(T, 3 * d, x.device))
             ops.rope_qk_(qkv, llm.cos, llm.sin, S, H, D)
-        else:
-            h1 = ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps)
-            if "qkv_rope" in lw:                                    # no adapters on q / k / v: RoPE in the GEMM's epilogue as in the frozen forward
-                qkv = ops.gemm_qkv_rope(h1, lw["qkv_rope"], llm.cos, llm.sin, S, H, D, out=ops.padded_rows(T, 3 * d, x.device))
-            else:
-                qkv = ops.gemm(h1, lw["qkv"], out=ops.padded_rows(T, 3 * d, x.device))
-                ops.rope_qk_(qkv, llm.cos, llm.sin, S, H, D)
         q5 = qkv.unflatten(0, (B, S)).unflatten(2, (3, H, D))
-        if "o_x" in lw:
-            ax, a2, t2 = _ext_rows(T, d, x.device)
-            attn, lse = ops.attention_fwd_lse(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], causal=True, key_valid=key_valid, out=a2.unflatten(0, (B, S)))
-            s["attnd"], s["t_o"] = _adapter_down(lora, pad["o"], a2, t2, seed + 3), t2
-            x_mid = ops.gemm(ax, lw["o_x"], residual=x)
-        else:
-            attn, lse = ops.attention_fwd_lse(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], causal=True, key_valid=key_valid)
-            x_mid = ops.gemm(attn.view(T, d), lw["o"], residual=x)
-        if "gu_x" in lw:
-            h2x, h2, t3 = _ext_rows(T, d, x.device)
-            ops.rmsnorm(x_mid, lw["ln2"], cfg.rms_norm_eps, out=h2)
-        else:
-            h2 = ops.rmsnorm(x_mid, lw["ln2"], cfg.rms_norm_eps)
+        pin = _ProjIn(lw, "o", T, d, x.device)
+        attn, lse = ops.attention_fwd_lse(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], causal=True, key_valid=key_valid,
+                                          out=pin.x.unflatten(0, (B, S)) if pin.ext else None)
+        x_mid = ops.gemm(pin.feed(lora, pad, s, seed + 3, attn.view(T, d)), pin.w, residual=x)
+        pin = _ProjIn(lw, "gu", T, d, x.device)                  # (a MoE layer with fused slabs reads h2 out of this buffer and extends its own slabs)
+        h2 = ops.rmsnorm(x_mid, lw["ln2"], cfg.rms_norm_eps, out=pin.x)
         s.update(qkv=qkv, attn=attn, lse=lse, x_mid=x_mid, seed=seed)
         if i in llm.moe_layers:
             x_out, l_aux = (_moe_fwd_ep if llm.ep is not None else _moe_fwd)(llm, lora, i, lw, pad, h2, x_mid, s, seed)
@@ -753,7 +760,7 @@ def forward_train(llm, embeds, key_valid):
             prune = _PRUNE_ROWS and needed is not None and i == len(llm.layers) - 1 and _SWIGLU_KEEP and (i, "ln2") not in lora.norm_names
             if prune:
                 llm.pruned_rows = int(needed[0].numel())                # the pruning HAPPENED (model_forward reports only this)
-            x_out = _dense_mlp_fwd(llm, lora, lw, pad, s, seed, h2, (h2x, t3) if "gu_x" in lw else None, x_mid, rows=needed[0] if prune else None)
+            x_out = _dense_mlp_fwd(llm, lora, lw, pad, s, seed, h2, pin, x_mid, rows=needed[0] if prune else None)
         saved.append(s)
         x = x_out
     out = ops.rmsnorm(x, llm.norm_w, cfg.rms_norm_eps)
@@ -761,11 +768,11 @@ def forward_train(llm, embeds, key_valid):
     return out.view(B, S, d), aux_sum, {"layers": saved, "x_last": x, "B": B, "S": S, "key_valid": key_valid}
 
 
-def _adapter_bwd(lora, ops_pad, dy, x, t, dx, seed, swiglu_gu=None, partials=False, defer_up=False, done=None, side_run=None):
-    """Gradients of one (fused) adapter: dB_pad [out, R], dA^T [in, R] (fp32) and dx += scaling * ((dy B) A) (through the dropout).  x = the
+def _adapter_bwd(lora, ops_pad, dy, ain, dx, seed, swiglu_gu=None, partials=False, defer_up=False, done=None, side_run=None):
+    """Gradients of one (fused) adapter: dB_pad [out, R], dA^T [in, R] (fp32) and dx += scaling * ((dy B) A) (through the dropout).  ain.x = the
     adapter's UNdropped input; the mask is regenerated from the seed wherever it is needed.  dx = None: nothing trainable lies in front of
     this adapter's input (the lowest layer of a decoder whose input rows are frozen) — only the two weight gradients are produced."""
-    A, AT, B, BT, R, _ = ops_pad
+    (x, t), AT, BT, R = ain, ops_pad.AT, ops_pad.BT, ops_pad.R
     # [T, 64] = scaling * dy B: the down-projection kernel with B^T as its matrix (reads dy once; no dropout on this side)
     # partials: the chunk partials are handed on unsummed (ops.SkinnyPartial) — the gradient unpack into the flat buffer adds them up itself
     partials = partials and R <= 32
@@ -816,42 +823,32 @@ def backward(llm, saved, d_hidden, d_aux=None, need_d_embeds=True):
     llm.ensure_positions(S)                                     # (forward_train grew the tables already; a no-op then)
     grads = {}
 
-    def take(i, ops_pad, dB, dAT):
-        """Unpack the fused pair's gradients into the per-target parameters -- straight into the parameters' .grad (the engine's flat
-        buffer) when a gradient sink is attached, one launch per adapter."""
-        for k, t in enumerate(ops_pad[5]):
-            nb, na = f"model.layers.{i}.{_module(t)}.lora_B.default.weight", f"model.layers.{i}.{_module(t)}.lora_A.default.weight"
-            pb, pa = lora.params[lora.index[nb]], lora.params[lora.index[na]]
-            direct = (lora.grad_sink is not None and pb.grad is not None and pa.grad is not None and pb.grad.is_contiguous() and pa.grad.is_contiguous()
-                      and pb.grad.dtype == torch.float32)
-            if direct and isinstance(dB, ops.SkinnyPartial) and isinstance(dAT, ops.SkinnyPartial):
-                ops.lora_grad_unpack_partials(dB, dAT, lora.rows[t], k * r, pb.grad, pa.grad)
-                continue
-            if isinstance(dB, ops.SkinnyPartial):
-                dB = dB.finish()
-            if isinstance(dAT, ops.SkinnyPartial):
-                dAT = dAT.finish()
-            if direct and dB.is_contiguous() and dAT.is_contiguous():
-                ops.lora_grad_unpack(dB, dAT, lora.rows[t], k * r, pb.grad, pa.grad)
-            else:
-                grads[nb] = dB[lora.rows[t], k * r:(k + 1) * r]
-                grads[na] = dAT[:, k * r:(k + 1) * r].t()
-
-    def take_e(i, ops_pad, dB, dAT):
-        """The same for the per-expert adapters of a MoE layer; dB / dAT: a list over all experts, or {global expert id: gradient} with
-        the experts this rank owns (expert parallelism)."""
-        for k, t in enumerate(ops_pad[5]):
-            for e, mod in enumerate(lora._modules_of(i, t)):
-                if isinstance(dB, dict) and e not in dB:
-                    continue
-                nb, na = f"model.layers.{i}.{mod}.lora_B.default.weight", f"model.layers.{i}.{mod}.lora_A.default.weight"
+    def take(i, ops_pad, items):
+        """Unpack fused pairs' gradients into the per-target parameters -- straight into the parameters' .grad (the engine's flat buffer) when a
+        gradient sink is attached, one launch per adapter.  items: [(e, dB, dAT)], e = index of the module among lora._modules_of(i, target):
+        one item with e = 0 for a dense group (the only one that may hand over unsummed chunk partials), one per expert for the MLP groups of a
+        MoE layer — under expert parallelism the experts this rank owns, by global id."""
+        items = [list(it) for it in items]
+        for k, t in enumerate(ops_pad.targets):
+            mods = lora._modules_of(i, t)
+            for it in items:
+                e, dB, dAT = it
+                nb, na = f"model.layers.{i}.{mods[e]}.lora_B.default.weight", f"model.layers.{i}.{mods[e]}.lora_A.default.weight"
                 pb, pa = lora.params[lora.index[nb]], lora.params[lora.index[na]]
-                if (lora.grad_sink is not None and pb.grad is not None and pa.grad is not None and pb.grad.is_contiguous() and pa.grad.is_contiguous()
-                        and pb.grad.dtype == torch.float32 and dB[e].is_contiguous() and dAT[e].is_contiguous()):
-                    ops.lora_grad_unpack(dB[e], dAT[e], lora.rows[t], k * r, pb.grad, pa.grad)
+                direct = (lora.grad_sink is not None and pb.grad is not None and pa.grad is not None and pb.grad.is_contiguous() and pa.grad.is_contiguous()
+                          and pb.grad.dtype == torch.float32)
+                if direct and isinstance(dB, ops.SkinnyPartial) and isinstance(dAT, ops.SkinnyPartial):
+                    ops.lora_grad_unpack_partials(dB, dAT, lora.rows[t], k * r, pb.grad, pa.grad)
+                    continue
+                if isinstance(dB, ops.SkinnyPartial):
+                    it[1] = dB = dB.finish()                       # (summed once: the group's next target reads the sum)
+                if isinstance(dAT, ops.SkinnyPartial):
+                    it[2] = dAT = dAT.finish()
+                if direct and dB.is_contiguous() and dAT.is_contiguous():
+                    ops.lora_grad_unpack(dB, dAT, lora.rows[t], k * r, pb.grad, pa.grad)
                 else:
-                    grads[nb] = dB[e][lora.rows[t], k * r:(k + 1) * r]
-                    grads[na] = dAT[e][:, k * r:(k + 1) * r].t()
+                    grads[nb] = dB[lora.rows[t], k * r:(k + 1) * r]
+                    grads[na] = dAT[:, k * r:(k + 1) * r].t()
 
     part_ok = lora.grad_sink is not None and _UNPACK_PARTIALS and lora.r <= 32      # the unpack into the flat gradient buffer sums the chunk partials itself
     # MP_LORA_WGRAD_STREAM=1: the dense layers' pure weight-gradient work (dA^T = drop(x)^T dt and the unpack into the flat gradient buffer: two
@@ -879,83 +876,84 @@ def backward(llm, saved, d_hidden, d_aux=None, need_d_embeds=True):
     def sink(i):
         pre = f"model.layers.{i}."
         ng = {n: grads.pop(n) for n in [k for k in grads if k.startswith(pre)]}
-        if side is not None and (ng or getattr(lora, "sink_reduces", True)):
+        if side is not None and (ng or lora.sink_reduces):
             torch.cuda.current_stream().wait_stream(side)          # the layer's gradients are complete before anything adds to or reduces them
             for g in ng.values():                                  # (side-stream allocations read on this stream from here on)
                 g.record_stream(torch.cuda.current_stream())
         lora.grad_sink(i, ng)
 
+    def adapter_step(k, dy, dx, seed, **form):
+        """Projection k's adapter, if its group has one, behind the dgrad dx = dy W of lw[k + "_T"]: dx gains the adapter's input gradient
+        (_adapter_bwd; form: the fused form this layer is eligible for) and the two weight gradients go to take() on the weight-gradient
+        stream.  Reads the layer the loop below is at (i, s, pad)."""
+        if k not in pad:
+            return dx
+        dx, dB, dAT = _adapter_bwd(lora, pad[k], dy, s["adapter_in"][k], dx, seed, partials=part_ok, side_run=wg if side is not None else None, **form)
+        wg(lambda: take(i, pad[k], [(0, dB, dAT)]), dB)
+        return dx
+
     dx = ops.rmsnorm_bwd(saved["x_last"], llm.norm_w, d_hidden.reshape(T, d).contiguous(), cfg.rms_norm_eps)
     for i in range(len(llm.layers) - 1, -1, -1):
         lw, s = llm.layers[i], saved["layers"][i]
         pad = s["pad"]
+        ln1_trains, ln2_trains = (i, "ln1") in lora.norm_names, (i, "ln2") in lora.norm_names
+        rows_last = s.get("rows_last")
+        up_late = None
         # ---- MLP: x_out = x_mid + down(act) [+ adapter], or the MoE layer
         if s.get("moe"):
-            d_h2 = (_moe_bwd_ep if s.get("ep") else _moe_bwd)(llm, lora, i, lw, s, dx, d_aux, grads, take_e)
+            d_h2 = (_moe_bwd_ep if s.get("ep") else _moe_bwd)(llm, lora, i, lw, s, dx, d_aux, grads, take)
         else:
-            rows_last = s.get("rows_last")
             dy_mlp = dx if rows_last is None else ops.gather_rows_bf16(dx, rows_last)      # the pruned last layer: its MLP saw these rows only
             d_act = ops.gemm(dy_mlp, lw["down_T"])
-            d_gu = None
-            gu_done = None                                      # (dB, dt) of the gate|up adapter when the one-kernel form below produced them
-            if ("down" in pad and "gu" in pad and _FUSE_SWSK and _FUSE_UP_SWIGLU and _FUSE_DY and pad["down"][4] <= 16 and pad["gu"][4] <= 32
-                    and d_act.stride(0) % 8 == 0 and dy_mlp.stride(0) % 8 == 0 and s["gu"].is_contiguous()):
-                # both adapters: the down adapter's two products of dy, its weight gradient over act, then ONE kernel from d_act to d gate|up
-                # that also takes the gate|up adapter's two products of it (the 225 MB tensor is written once and not read back)
-                _, ATd, _, BTd, Rd, _ = pad["down"]
-                _, _, _, BTg, Rg, _ = pad["gu"]
-                sd = s["seed"] + 1
-                dBd, dtd = ops.tn_skinny_down(dy_mlp, s["t_d"], BTd, Rd, lora.scaling, lora.scaling, reduce=not part_ok)
-                kbd = lora.keep_bits.get(sd)
-                wg(lambda: take(i, pad["down"], dBd, ops.tn_skinny(s["actd"], dtd, Rd, 1.0, lora.p_active, sd, reduce=not part_ok, keep_bits=kbd)), dBd, dtd)
-                d_gu, dBg, dtg = ops.swiglu_bwd_skinny(dtd, ATd, d_act, s["gu"], Rd, lora.p_active, sd, s["t_gu"], BTg, Rg, lora.scaling, lora.scaling,
-                                                       reduce=not part_ok, keep_bits=kbd)
-                gu_done, d_act = (dBg, dtg), None
-            elif "down" in pad:
-                fused = _FUSE_UP_SWIGLU and pad["down"][4] <= 32 and d_act.stride(0) % 8 == 0
-                d_act, dB, dAT = _adapter_bwd(lora, pad["down"], dy_mlp, s["actd"], s["t_d"], d_act, s["seed"] + 1, swiglu_gu=s["gu"] if fused else None, partials=part_ok,
-                                              side_run=wg if side is not None else None)
-                wg(lambda: take(i, pad["down"], dB, dAT), dB)
-                if fused:
-                    d_gu, d_act = d_act, None
-            if d_gu is None:
-                d_gu = ops.swiglu_pair_bwd(s["gu"], d_act)
+            sd = s["seed"] + 1
+            # which forms this layer's two adapters take (the dgrad results' strides are part of the tests, hence after the GEMM)
+            one_kernel = ("down" in pad and "gu" in pad and _FUSE_SWSK and _FUSE_UP_SWIGLU and _FUSE_DY and pad["down"].R <= 16 and pad["gu"].R <= 32
+                          and d_act.stride(0) % 8 == 0 and dy_mlp.stride(0) % 8 == 0 and s["gu"].is_contiguous())
+            up_into_swiglu = not one_kernel and "down" in pad and _FUSE_UP_SWIGLU and pad["down"].R <= 32 and d_act.stride(0) % 8 == 0
             # the lowest layer with frozen input rows: nothing trainable reads anything in front of the gate|up input unless the attention
             # projections carry adapters or a norm of this layer trains
             stop_here = (i == 0 and not need_d_embeds and "o" not in pad and "qkv" not in pad and rows_last is None
-                         and (i, "ln1") not in lora.norm_names and (i, "ln2") not in lora.norm_names)
+                         and not ln1_trains and not ln2_trains)
+            gu_done = None                                      # (dB, dt) of the gate|up adapter when the one-kernel form produced them
+            if one_kernel:
+                # both adapters: the down adapter's two products of dy, its weight gradient over act, then ONE kernel from d_act to d gate|up
+                # that also takes the gate|up adapter's two products of it (the 225 MB tensor is written once and not read back)
+                dn, ain = pad["down"], s["adapter_in"]
+                dBd, dtd = ops.tn_skinny_down(dy_mlp, ain["down"].t, dn.BT, dn.R, lora.scaling, lora.scaling, reduce=not part_ok)
+                kbd = lora.keep_bits.get(sd)
+                wg(lambda: take(i, dn, [(0, dBd, ops.tn_skinny(ain["down"].x, dtd, dn.R, 1.0, lora.p_active, sd, reduce=not part_ok, keep_bits=kbd))]), dBd, dtd)
+                d_gu, dBg, dtg = ops.swiglu_bwd_skinny(dtd, dn.AT, d_act, s["gu"], dn.R, lora.p_active, sd, ain["gu"].t, pad["gu"].BT, pad["gu"].R,
+                                                       lora.scaling, lora.scaling, reduce=not part_ok, keep_bits=kbd)
+                gu_done = (dBg, dtg)
+            elif up_into_swiglu:                                # the down adapter's input gradient and the SwiGLU backward in one pass: d gate|up comes back
+                d_gu = adapter_step("down", dy_mlp, d_act, sd, swiglu_gu=s["gu"])
+            else:
+                d_gu = ops.swiglu_pair_bwd(s["gu"], adapter_step("down", dy_mlp, d_act, sd))
             d_h2 = None if stop_here else ops.gemm(d_gu, lw["gu_T"])
-            up_late = None
-            if "gu" in pad:
-                # the adapter's input gradient has one reader, the post-attention norm's backward below: that kernel adds it on its way in
-                defer = (_FUSE_NORM_UP and not stop_here and rows_last is None and d == 4096 and (i, "ln2") not in lora.norm_names
-                         and pad["gu"][4] <= 16 and d_h2.stride(0) % 8 == 0)
-                d_h2, dB, dAT = _adapter_bwd(lora, pad["gu"], d_gu, s["h2d"], s["t_gu"], d_h2, s["seed"], partials=part_ok, defer_up=defer, done=gu_done,
-                                             side_run=wg if side is not None else None)
-                if defer:
-                    d_h2, up_late = d_h2
-                wg(lambda: take(i, pad["gu"], dB, dAT), dB)
+            # the gate|up adapter's input gradient has one reader, the post-attention norm's backward below: that kernel adds it on its way in
+            defer = ("gu" in pad and _FUSE_NORM_UP and not stop_here and rows_last is None and d == 4096 and not ln2_trains
+                     and pad["gu"].R <= 16 and d_h2.stride(0) % 8 == 0)
+            d_h2 = adapter_step("gu", d_gu, d_h2, s["seed"], defer_up=defer, done=gu_done)
+            if defer:
+                d_h2, up_late = d_h2
             if stop_here:
                 dx = None
                 if lora.grad_sink is not None:
                     sink(i)
                 break
-        if s.get("rows_last") is not None:
+        if rows_last is not None:
             # compact rows back into the layer's full gradient: every other row of dx is zero and stays zero (no MLP branch, no residual)
             d_mid_c = ops.rmsnorm_bwd(s["xm_c"], lw["ln2"], d_h2, cfg.rms_norm_eps, add=dy_mlp)
-            d_mid = ops.scatter_rows_bf16_(dx, s["rows_last"], d_mid_c)
-        elif (i, "ln2") in lora.norm_names:
+            d_mid = ops.scatter_rows_bf16_(dx, rows_last, d_mid_c)
+        elif ln2_trains:
             d_mid, grads[lora.norm_names[(i, "ln2")]] = ops.rmsnorm_bwd(s["x_mid"], lw["ln2"], d_h2, cfg.rms_norm_eps, add=dx, want_wgrad=True)
-        elif not s.get("moe") and up_late is not None:
+        elif up_late is not None:
             dt_, AT_, R_, p_, seed_, kb_ = up_late
             d_mid = ops.rmsnorm_bwd_up(s["x_mid"], lw["ln2"], d_h2, cfg.rms_norm_eps, dt_, AT_, R_, p_, seed_, add=dx, keep_bits=kb_)
         else:
             d_mid = ops.rmsnorm_bwd(s["x_mid"], lw["ln2"], d_h2, cfg.rms_norm_eps, add=dx)
         # ---- attention: x_mid = x + o(attn(rope(qkv(rmsnorm(x))))) [+ adapters on o and on q / k / v]
-        d_attn = ops.gemm(d_mid, lw["o_T"])
-        if "o" in pad:
-            d_attn, dB, dAT = _adapter_bwd(lora, pad["o"], d_mid, s["attnd"], s["t_o"], d_attn, s["seed"] + 3, partials=part_ok, side_run=wg if side is not None else None)
-            wg(lambda: take(i, pad["o"], dB, dAT), dB)
+        d_attn = adapter_step("o", d_mid, ops.gemm(d_mid, lw["o_T"]), s["seed"] + 3)
         q5 = s["qkv"].unflatten(0, (B, S)).unflatten(2, (3, H, D))
         # the transpose of a rotation is the rotation by -theta: the attention backward stores dq / dk rotated (same bits as mp_rope_qk_bf16 on its result)
         rot = _ROPE_IN_ATTN_BWD and D == 128 and s["attn"].stride(-2) % 8 == 0
@@ -964,11 +962,8 @@ def backward(llm, saved, d_hidden, d_aux=None, need_d_embeds=True):
         dqkv = dqkv.flatten(0, 1).flatten(1)                    # [T, 3d] view of the (row-padded) buffer
         if not rot:
             ops.rope_qk_(dqkv, llm.cos, llm.sin_neg, S, H, D)
-        d_h1 = ops.gemm(dqkv, lw["qkv_T"])
-        if "qkv" in pad:
-            d_h1, dB, dAT = _adapter_bwd(lora, pad["qkv"], dqkv, s["h1d"], s["t_qkv"], d_h1, s["seed"] + 2, partials=part_ok, side_run=wg if side is not None else None)
-            wg(lambda: take(i, pad["qkv"], dB, dAT), dB)
-        if (i, "ln1") in lora.norm_names:
+        d_h1 = adapter_step("qkv", dqkv, ops.gemm(dqkv, lw["qkv_T"]), s["seed"] + 2)
+        if ln1_trains:
             dx, grads[lora.norm_names[(i, "ln1")]] = ops.rmsnorm_bwd(s["x"], lw["ln1"], d_h1, cfg.rms_norm_eps, add=d_mid, want_wgrad=True)
         else:
             dx = ops.rmsnorm_bwd(s["x"], lw["ln1"], d_h1, cfg.rms_norm_eps, add=d_mid)

@@ -6,8 +6,11 @@ scalar argument or a pointer that became None shows up here by name.
 The fixture is this module's own output at the commit written inside it (`python tests/test_gpu_launch_trace.py --record PATH [--commit HASH]`);
 the stacks seed their weights from a device generator and every input below from a CPU generator, so the bytes reproduce.  Regenerate it only
 with a change that is MEANT to alter a launch sequence, from the parent of that change.  The two once-per-process workspace registrations are left
-out of the lists (whether they happen inside a case depends on what ran before it).  The expert-parallel branch needs more than one rank and is
-covered where ranks are available."""
+out of the lists (whether they happen inside a case depends on what ran before it).
+
+The training cases cover the dense adapters (MLP targets; all seven targets at r = 16 and at r = 8 with dropout; frozen input rows; trainable norms;
+a gradient sink with and without the weight-gradient stream; d = 4096 for the up-projection deferred into the norm backward) and the MoE layers
+(top-1 with and without dropout, top-2, and the expert-parallel branch on a one-rank group, whose exchanges are identities)."""
 import contextlib
 import hashlib
 import json
@@ -153,33 +156,76 @@ def _folded_case(dev):
     return calls, {"hidden": _sha(out), "aux": _sha(torch.cat([a.reshape(1) for a in aux]))}, {"folded_layers": llm.folded_layers, "pruned_rows": llm.pruned_rows}
 
 
-def _train_case(needed):
+def _train_case(needed=None, kind="dense", cfg=None, targets=("gate_proj", "up_proj", "down_proj"), r=8, dropout=0.0, sft_modules=(), need_d_embeds=True,
+                sink=False, wgrad_stream=False, d_aux=False, ep=False):
+    """forward_train + backward.  cfg: a callable that builds the config (default: the tiny one of `kind`); sink: the parameters' .grad preallocated
+    and a gradient sink attached (the .grad tensors are hashed, and the sink's calls go into the state); wgrad_stream: llama_lora._WGRAD_STREAM for the
+    pass; d_aux: the MoE layers' l_aux gradient given; ep: a one-rank expert-parallel group (the exchanges are identities)."""
     def run(dev):
         from medplib_amd.model import llama_lora
-        cfg = _cfg("dense")
-        llm = _stack(dev, cfg)
-        lora = llama_lora.enable_lora(llm, cfg, r=8, alpha=16, dropout=0.0, targets=("gate_proj", "up_proj", "down_proj"))
-        g = torch.Generator().manual_seed(31)
-        for n, p in zip(lora.names, lora.params):
-            p.data.copy_((torch.randn(p.shape, generator=g) * (0.05 if "lora_A" in n else 0.03)).to(torch.bfloat16).float().to(dev))
-        x = _embeds(dev, B_ROWS, S_ROWS, cfg.hidden_size)
-        dy = _embeds(dev, B_ROWS, S_ROWS, cfg.hidden_size, seed=3)
-        if needed is not None:
-            mask = torch.zeros(B_ROWS * S_ROWS, dtype=torch.uint8)
-            mask[list(needed)] = 1
-            llm.needed_rows = (mask.nonzero().flatten().to(dev), mask.to(dev))
-            dy = dy * mask.view(B_ROWS, S_ROWS, 1).to(dev).to(dy.dtype)       # nothing reads the other rows: their gradient is zero
-        with torch.no_grad(), _traced() as calls:
-            out, aux_sum, saved = llama_lora.forward_train(llm, x, None)
-            grads = llama_lora.backward(llm, saved, dy)
-        llm.needed_rows = None
-        sha = {"hidden": _sha(out)}
-        sha.update({"grad:" + n: _sha(grads[n]) for n in sorted(grads)})
-        return calls, sha, {"pruned_rows": llm.pruned_rows, "gate_pass": llm.gate_pass, "grads": len(grads)}
+        c = cfg() if cfg is not None else _cfg(kind)
+        llm = _stack(dev, c)
+        comm = None
+        if ep:
+            from medplib_amd.comm import RcclComm
+            from medplib_amd.expert_parallel import ExpertParallel
+            comm = RcclComm(rank=0, world=1)
+        try:
+            if ep:
+                llm.enable_expert_parallel(ExpertParallel(None, 1, c.num_experts, capi_comm=comm))
+            lora = llama_lora.enable_lora(llm, c, r=r, alpha=16, dropout=dropout, targets=targets, sft_modules=sft_modules)
+            llm.training = True
+            g = torch.Generator().manual_seed(31)
+            for n, p in zip(lora.names, lora.params):
+                p.data.copy_((torch.randn(p.shape, generator=g) * (0.05 if "lora_A" in n else 0.03)).to(torch.bfloat16).float().to(dev))
+            x = _embeds(dev, B_ROWS, S_ROWS, c.hidden_size)
+            dy = _embeds(dev, B_ROWS, S_ROWS, c.hidden_size, seed=3)
+            if needed is not None:
+                mask = torch.zeros(B_ROWS * S_ROWS, dtype=torch.uint8)
+                mask[list(needed)] = 1
+                llm.needed_rows = (mask.nonzero().flatten().to(dev), mask.to(dev))
+                dy = dy * mask.view(B_ROWS, S_ROWS, 1).to(dev).to(dy.dtype)       # nothing reads the other rows: their gradient is zero
+            handed = []
+            if sink:
+                for p in lora.params:
+                    p.grad = torch.zeros(p.shape, dtype=torch.float32, device=dev)
+                lora.grad_sink = lambda i, ng: handed.append((i, ng))
+            aux_grad = torch.tensor([0.01], dtype=torch.float32, device=dev) if d_aux else None
+            was = llama_lora._WGRAD_STREAM
+            llama_lora._WGRAD_STREAM = wgrad_stream
+            try:
+                with torch.no_grad(), _traced() as calls:
+                    out, aux_sum, saved = llama_lora.forward_train(llm, x, None)
+                    grads = llama_lora.backward(llm, saved, dy, aux_grad, need_d_embeds=need_d_embeds)
+            finally:
+                llama_lora._WGRAD_STREAM = was
+            llm.needed_rows = None
+            sha = {"hidden": _sha(out)}
+            sha.update({"grad:" + n: _sha(grads[n]) for n in sorted(grads) if grads[n] is not None})
+            state = {"pruned_rows": llm.pruned_rows, "gate_pass": llm.gate_pass, "grads": len(grads)}
+            if d_aux:
+                sha["aux_sum"] = _sha(aux_sum)
+            if sink:
+                sha.update({"param.grad:" + n: _sha(p.grad) for n, p in zip(lora.names, lora.params)})
+                sha.update({f"sink:{i}:{n}": _sha(t) for i, ng in handed for n, t in ng.items()})
+                state["sink"] = [[i, sorted(ng)] for i, ng in handed]
+            if not need_d_embeds:
+                state["d_embeds_is_none"] = grads["__d_embeds__"] is None
+            return calls, sha, state
+        finally:
+            if comm is not None:
+                comm.close()
     return run
 
 
+def _d4096_one_layer():
+    from medplib_amd.model.config import MedPLIBConfig
+    return MedPLIBConfig.medplib_7b(num_hidden_layers=1, vocab_size=1024, moe_enable=False)
+
+
 FEW_ROWS = (3, 11, 25)
+ALL_TARGETS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+MLP_AND_QV = ("gate_proj", "up_proj", "down_proj", "q_proj", "v_proj")
 
 CASES = {
     "forward-dense": _forward_case("dense"),
@@ -194,6 +240,17 @@ CASES = {
     "folded-norms": _folded_case,
     "train-dense-adapters": _train_case(None),
     "train-dense-adapters-needed-rows": _train_case(FEW_ROWS),
+    "train-dense-all-targets-r16": _train_case(targets=ALL_TARGETS, r=16),                     # qkv R = 48 -> 64 (the R > 32 fallbacks), gu R = 32, o / down R = 16
+    "train-dense-all-targets-r8-dropout": _train_case(targets=ALL_TARGETS, dropout=0.1),       # keep-bits at K = 256, refused at K = 320; qkv R = 24 -> 32
+    "train-dense-frozen-inputs": _train_case(need_d_embeds=False),                             # layer 0 stops at the gate|up gradient
+    "train-dense-norms-trainable": _train_case(FEW_ROWS, sft_modules=("input_layernorm", "post_attention_layernorm")),     # ln2 trains: no pruning
+    "train-dense-grad-sink": _train_case(sink=True),                                           # chunk partials unpacked straight into .grad
+    "train-dense-grad-sink-wgrad-stream": _train_case(sink=True, wgrad_stream=True),           # the same launches in host order, on two queues
+    "train-top1-adapters": _train_case(kind="top1", d_aux=True),                               # fused capacity slabs, gate backward, d wg
+    "train-top1-adapters-dropout": _train_case(kind="top1", d_aux=True, dropout=0.1),          # per-expert seeds
+    "train-top2-adapters": _train_case(kind="top2", d_aux=True),
+    "train-top1-expert-parallel-one-rank": _train_case(kind="top1", d_aux=True, dropout=0.1, ep=True, targets=MLP_AND_QV),
+    "train-dense-d4096-one-layer": _train_case(cfg=_d4096_one_layer),                          # d == 4096: the deferred up-projection in the norm backward
 }
 for _kind in ("dense", "top1", "top2"):
     for _B in (1, 2):
