@@ -204,6 +204,29 @@ int mp_argmax_rows_f32(const float* x, int64_t ld, int64_t rows, int cols, int64
  * picks.  0 < cols <= 65536 and 0 < inv_temperature < inf, else MP_ERR_SHAPE before any launch; null operands MP_ERR_ARG. */
 int mp_sample_rows_f32(const float* logits, int64_t ld, int64_t rows, int cols, float inv_temperature, const float* u, int64_t* out,
                        hipStream_t stream);
+/* mp_sample_rows_f32 over a truncated distribution: HF 4.31's warper chain TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper
+ * with its defaults (filter value -inf, min_tokens_to_keep = 1) in front of the multinomial pick — what the reference's
+ * generate(do_sample=True, temperature=, top_p=) of vqa_infer.py:430-442 runs, GenerationConfig.top_k = 50 included.  Per row, with the
+ * weights w of mp_sample_rows_f32 (1 at the maximum, 0 past `cols`, NaN columns weigh nothing):
+ *   top-k (0 < top_k < cols; otherwise none): t_k = the top_k-th largest logit counting multiplicity (the smallest one when the row has
+ *     fewer than top_k non-NaN columns); the survivors are the columns with l >= t_k, so ties at t_k all survive (HF: scores <
+ *     topk[..., -1] are removed).  The selection compares the logits themselves: no arithmetic, exact.  NaN columns never survive.
+ *   top-p (top_p < 1), over the survivors: Z = sum of w, A(t) = sum of w over survivors with l <= t; a survivor is kept iff
+ *     A(l) / Z > 1 - top_p, and the group of the maximum always (what top_p = 0 leaves).  Columns with equal logits share one fate (HF's
+ *     unstable sort would split such a group arbitrarily).  A and Z are fp32 sums in one fixed order: within a few 1e-7 of float64.
+ *   pick: the inverse CDF of mp_sample_rows_f32 over the kept columns in column order: the smallest kept i with w_i > 0 and
+ *     C_kept(i) > u * C_kept(last); when none qualifies (u >= 1, rounding, NaN u) the last kept column with w > 0.  Never an unkept column.
+ * The kept columns are exactly those with l >= cut[r], cut[r] = the smallest kept logit, and kept[r] counts them; a row without a
+ * maximum above -inf keeps nothing: token 0, kept 0, cut +inf.  kept and cut may be null.
+ * Filters off (no top-k and top_p = 1): `out` is written by mp_sample_rows_f32 itself — the same token bit for bit — and only a caller that
+ * passes kept or cut pays a second launch, which fills those two.  Otherwise one launch, no workspace, no host read: it can be captured.
+ * No atomics, every reduction in a fixed order: the same row, u, T, k and p give the same token and cut on every launch, alone or beside
+ * other rows, for every alignment of the row.
+ * 0 < cols <= 65536, rows >= 0, 0 < inv_temperature < inf, 0 <= top_p <= 1 (NaN refused), top_k >= 0, and the ld rule of
+ * mp_sample_rows_f32 (ld = 0: one row against every u), else MP_ERR_SHAPE before any launch; null logits / u / out MP_ERR_ARG. */
+int mp_sample_filtered_rows_f32(const float* logits, int64_t ld, int64_t rows, int cols, float inv_temperature, int top_k, float top_p,
+                                const float* u, int64_t* out, int* kept /* nullable [rows] */, float* cut /* nullable [rows] */,
+                                hipStream_t stream);
 /* out = silu(gu[:, :ff]) * gu[:, ff:]  (LlamaMLP). */
 int mp_swiglu_bf16(const void* gu, int64_t ldgu, void* out, int64_t ldo, int64_t rows, int ff, hipStream_t stream);
 int mp_cast_f32_to_bf16(const float* x, void* y, int64_t n, hipStream_t stream);

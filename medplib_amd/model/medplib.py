@@ -62,11 +62,16 @@ class _SamplePick:
     """The sampling next-token pick of generate_stream: token `step` of a request is ops.sample_rows at the uniform the keyed generator
     draws under (seed, step).  `step` is an int (the first token, the token-by-token loop) or an int32 [1] device counter (the captured
     decode step: every replay draws what the loop draws for that token).  An injected `uniforms(step) -> float` replaces the generator; it
-    runs on the host, so it cannot be captured.  last_u: the [1] tensor of the latest draw (inside a captured step: the graph's own buffer)."""
+    runs on the host, so it cannot be captured.  last_u: the [1] tensor of the latest draw (inside a captured step: the graph's own buffer).
+    top_k / top_p truncate the distribution first (ops.sample_rows_filtered: HF's top-k, then top-p); with both off (0 and 1.0) the pick is
+    ops.sample_rows as before.  Temperature, top_k and top_p are launch constants of a captured step."""
     needs_step = True                        # the captured step keeps the number of the generated token on the device
 
-    def __init__(self, temperature, seed, device, uniforms=None):
+    def __init__(self, temperature, seed, device, uniforms=None, top_k=0, top_p=1.0):
         self.temperature, self.seed, self.device, self.uniforms, self.last_u = float(temperature), int(seed), device, uniforms, None
+        self.top_k, self.top_p = int(top_k), float(top_p)
+        if self.top_k < 0 or not 0.0 <= self.top_p <= 1.0:
+            raise ValueError(f"sampling: top_k={top_k} must not be negative and top_p={top_p} must lie in [0, 1]")
 
     def __call__(self, logits, step):
         if self.uniforms is not None:
@@ -76,7 +81,9 @@ class _SamplePick:
         else:
             u = ops.sample_uniform(self.seed, int(step), self.device)
         self.last_u = u
-        return ops.sample_rows(logits, u, self.temperature)
+        if self.top_k == 0 and self.top_p >= 1.0:
+            return ops.sample_rows(logits, u, self.temperature)
+        return ops.sample_rows_filtered(logits, u, self.temperature, self.top_k, self.top_p)
 
 
 class _VisualModel(nn.Module):
@@ -903,13 +910,13 @@ class MedPLIBForCausalLM(nn.Module):
             last = h[0, -1:]
 
     def _greedy(self, ids, images_clip, max_new_tokens, eos_token_id, mask_images=None, image_token_types=None, image_token_lengths=None,
-                region_masks=None, valid_region_masks_bool=None):
+                region_masks=None, valid_region_masks_bool=None, pick=_argmax_pick):
         """HF `generate(do_sample=False, use_cache=True)` on one sample (MedPLIB.py:592-606; prepare_inputs_for_generation,
         medplib_moe_llama.py:451-485): prefill of the spliced prompt, then single-token decode steps against the KV cache (_decode).
         Returns (output_ids [1, L + n] on the host, [hidden states of the prompt, of each fed token])."""
         generated, hiddens = [], []
         for generated, _, hiddens in self._decode(ids, images_clip, max_new_tokens, (eos_token_id,), mask_images, image_token_types,
-                                                  image_token_lengths, region_masks, valid_region_masks_bool):
+                                                  image_token_lengths, region_masks, valid_region_masks_bool, pick=pick):
             pass
         return np.concatenate([ids, np.asarray(generated, dtype=np.int64)[None]], 1), list(hiddens)
 
@@ -921,7 +928,8 @@ class MedPLIBForCausalLM(nn.Module):
         # HF generate kwargs the reference driver passes (vqa_infer.py:430-442): accepted when they mean greedy decoding, refused
         # loudly otherwise — sampling and beam search are not built
         if kwargs.get("do_sample") or (kwargs.get("temperature") or 0) > 0 and kwargs.get("do_sample") is not False:
-            raise NotImplementedError("generate(): sampling (do_sample / temperature > 0) is not built; the shipped eval scripts decode greedily")
+            raise NotImplementedError("generate(): sampling (do_sample / temperature > 0) is not built here: call generate_sample() "
+                                      "(temperature, top-k, top-p); the shipped eval scripts decode greedily")
         if (kwargs.get("num_beams") or 1) != 1:
             raise NotImplementedError("generate(): beam search (num_beams > 1) is not built; the shipped eval scripts use num_beams=1")
         unknown = set(kwargs) - {"do_sample", "temperature", "top_p", "num_beams", "use_cache", "mask_images", "image_token_types",
@@ -929,7 +937,12 @@ class MedPLIBForCausalLM(nn.Module):
                                  "return_dict_in_generate", "pad_token_id"}
         if unknown:
             raise TypeError(f"generate(): unsupported arguments {sorted(unknown)}")
-        self._require_shadowable("generate")
+        return self._generate_rows("generate", input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs, lambda b: _argmax_pick)
+
+    def _generate_rows(self, who, input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs, pick_of_row):
+        """generate() / generate_sample(): batch rows decoded one after the other, row b's next token chosen by pick_of_row(b); output ids
+        [B, L + n_max], prompt included, right-padded with eos."""
+        self._require_shadowable(who)
         self.sync_side_streams()
         ids = _np_ids(input_ids).astype(np.int64)
         was_training = self.training
@@ -948,16 +961,41 @@ class MedPLIBForCausalLM(nn.Module):
                     before = sum(1 for v in rv[:b] if any(v))
                     rm, rv = (rm[before:before + 1] if any(rv[b]) else ()), rv[b:b + 1]
                 out, _ = self._greedy(row, img, max_new_tokens, eos_token_id, kwargs.get("mask_images"), kwargs.get("image_token_types"),
-                                      kwargs.get("image_token_lengths"), rm, rv)
+                                      kwargs.get("image_token_lengths"), rm, rv, pick=pick_of_row(b))
                 rows.append(out[0])
         self.train(was_training)
         n = max(r.shape[0] for r in rows)
         return torch.from_numpy(np.stack([np.concatenate([r, np.full(n - r.shape[0], eos_token_id, np.int64)]) for r in rows]))
 
     @torch.no_grad()
+    def generate_sample(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, temperature=1.0, top_k=50,
+                        top_p=1.0, sample_seed=None, **kwargs):
+        """generate() with HF's do_sample=True (what vqa_infer.py:430-442 asks for with --temperature > 0): every next token is drawn from
+        softmax(logits / temperature) truncated by top-k, then top-p (HF 4.31's TemperatureLogitsWarper -> TopKLogitsWarper ->
+        TopPLogitsWarper; top_k = 50 is its GenerationConfig default, top_p=None means 1.0), by inverse CDF at the keyed generator's
+        uniforms (_SamplePick, ops.sample_rows_filtered): HF's distribution, not torch.multinomial's draws.  Row b draws under seed
+        sample_seed + b; sample_seed=None takes one from torch's global generator, as the serving worker does, so torch.manual_seed makes
+        a run repeatable.  Same return layout as generate(): prompt included, right-padded with eos.  temperature <= 0 raises ValueError
+        as HF does; beam search and repetition penalty are not built."""
+        if not float(temperature) > 0:
+            raise ValueError(f"generate_sample(): temperature={temperature} has to be a strictly positive float (greedy decoding: generate())")
+        if (kwargs.get("num_beams") or 1) != 1:
+            raise NotImplementedError("generate_sample(): beam search (num_beams > 1) is not built; the shipped eval scripts use num_beams=1")
+        unknown = set(kwargs) - {"do_sample", "num_beams", "use_cache", "mask_images", "image_token_types", "image_token_lengths", "region_masks",
+                                 "valid_region_masks_bool", "output_hidden_states", "return_dict_in_generate", "pad_token_id"}
+        if unknown:
+            raise TypeError(f"generate_sample(): unsupported arguments {sorted(unknown)}")
+        if kwargs.get("do_sample") is False:
+            raise ValueError("generate_sample(): do_sample=False asks for greedy decoding: call generate()")
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,))) if sample_seed is None else int(sample_seed)
+        top_k, top_p = int(top_k or 0), 1.0 if top_p is None else float(top_p)
+        return self._generate_rows("generate_sample", input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs,
+                                   lambda b: _SamplePick(temperature, seed + b, self.device_, top_k=top_k, top_p=top_p))
+
+    @torch.no_grad()
     def generate_stream(self, input_ids, images_clip, images=None, temperature=1.0, top_p=1.0, max_new_tokens=256, stop_token_id=None,
                         eos_token_id=2, stream_interval=1, sample_seed=0, resize_list=None, original_size_list=None, region_masks=(),
-                        valid_region_masks_bool=(), attention_mask=None, uniforms=None, debug=None, stop_check=None):
+                        valid_region_masks_bool=(), attention_mask=None, uniforms=None, debug=None, stop_check=None, top_k=0, apply_top_p=False):
         """The serving worker's token loop (model/serve/model_worker.py generate_stream) on one sample, as a generator: prefill, then one
         decode step per token, yielding (new token ids so far, stopped, pred_mask) after tokens i with i % stream_interval == 0, after the
         last one (i == max_new_tokens - 1) and at a stop (eos_token_id, stop_token_id, or stop_check(ids) -> True at a yield: the worker's
@@ -965,8 +1003,10 @@ class MedPLIBForCausalLM(nn.Module):
 
         temperature < 1e-4: greedy, the tokens of generate().  Otherwise token i is drawn from softmax(logits / temperature) by inverse CDF
         (ops.sample_rows) at the uniform the keyed generator gives for (sample_seed, i) (ops.sample_uniform): one seed, one answer; the
-        stream matches torch.multinomial in distribution, not draw by draw.  top_p is accepted and IGNORED: the reference's worker reads
-        it from the request and never uses it.
+        stream matches torch.multinomial in distribution, not draw by draw.  apply_top_p=False (the default): top_p is accepted and
+        IGNORED, as is top_k — the reference's worker reads top_p from the request and never uses it.  apply_top_p=True: the distribution
+        is truncated before the draw by top_k (0: none), then top_p, as HF's warpers do (ops.sample_rows_filtered), in the loop and in the
+        captured step alike.
         Decode path (last_decode_path): the captured graph when decode_with_graph and _graph_decode_ok() hold, max_new_tokens > 2 and no
         `uniforms` is injected; the draw and the pick are then part of the captured step, and the host looks at the ids (and the cache's error
         word) only at the yields.  Otherwise the token-by-token loop.  uniforms(i) -> float replaces the generator (tests); it runs on the
@@ -983,7 +1023,12 @@ class MedPLIBForCausalLM(nn.Module):
             ids = ids[:, _np_ids(attention_mask)[0].astype(bool)]
         max_new_tokens, every = int(max_new_tokens), max(1, int(stream_interval))
         assert max_new_tokens >= 1
-        pick = _argmax_pick if temperature < 1e-4 else _SamplePick(temperature, sample_seed, self.device_, uniforms)
+        if temperature < 1e-4:
+            pick = _argmax_pick
+        elif apply_top_p:
+            pick = _SamplePick(temperature, sample_seed, self.device_, uniforms, top_k=top_k, top_p=1.0 if top_p is None else top_p)
+        else:
+            pick = _SamplePick(temperature, sample_seed, self.device_, uniforms)
         stop_ids = {int(t) for t in (eos_token_id, stop_token_id) if t is not None}
         due = lambda i: i % every == 0 or i == max_new_tokens - 1            # noqa: E731  the reference's condition on the token number
         looks = [i + 1 for i in range(max_new_tokens) if due(i)]

@@ -918,6 +918,21 @@ def sample_rows(logits, u, temperature):
     return out
 
 
+def sample_rows_filtered(logits, u, temperature, top_k=0, top_p=1.0, want_cut=False):
+    """sample_rows over the distribution truncated by top-k, then top-p (mp_sample_filtered_rows_f32: HF's Temperature -> TopK -> TopP warper
+    chain in front of the pick).  top_k = 0 or >= cols: no top-k; top_p = 1: no top-p; both off: sample_rows' tokens, bit for bit.
+    -> int64 [rows], or with want_cut (tokens, kept int32 [rows], cut fp32 [rows]): the kept columns are those with logit >= cut."""
+    _chk(logits, torch.float32, "sample_rows_filtered.logits"); _chk(u, torch.float32, "sample_rows_filtered.u")
+    assert logits.dim() == 2 and logits.stride(1) == 1 and u.dim() == 1 and u.is_contiguous() and u.numel() == logits.shape[0]
+    rows = logits.shape[0]
+    out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    kept = torch.empty(rows, dtype=torch.int32, device=logits.device) if want_cut else None
+    cut = torch.empty(rows, dtype=torch.float32, device=logits.device) if want_cut else None
+    lib().call("mp_sample_filtered_rows_f32", _p(logits), logits.stride(0), rows, logits.shape[1], 1.0 / float(temperature), int(top_k),
+               float(top_p), _p(u), _p(out), _p(kept), _p(cut), _stream())
+    return (out, kept, cut) if want_cut else out
+
+
 def sample_uniform(seed, step, device):
     """The uniform that picks generated token `step` of a request: the keyed generator of the gate draws under key (seed, step); fp32 [1]
     in [2^-25, 1] (1.0 itself with probability 2^-24: include/medplib_hip.h)."""

@@ -10,7 +10,8 @@ What the reference driver does with the model, in order, and where this harness 
 max_new_tokens=, tokenizer=, attention_mask=, mask_images=, image_token_types=, image_token_lengths=)` (:528-540), threshold 0.1,
 IoU / Dice meters, per-modality table (:565-633) | `--eval_vqa`: per sample `model.generate(input_ids, images=, attention_mask=,
 mask_images=, image_token_types=, do_sample=, temperature=, top_p=, num_beams=, max_new_tokens=, use_cache=True)` (:430-442), one
-JSON line per answer (:470-480).  The prompt is cut after the last ':' token (id 29901 with the Llama tokenizer, :426-428,521-523).
+JSON line per answer (:470-480); with `--temperature` above 0 the call is `model.generate_sample(..., temperature=, top_k=50, top_p=)`,
+the sampling HF runs for do_sample=True.  The prompt is cut after the last ':' token (id 29901 with the Llama tokenizer, :426-428,521-523).
 
 `FLAG_TABLE` holds the reference's command line as data.  Additions of this build: `--dataset synthetic` (seeded single-sample
 batches; no dataset / tokenizer files exist on the build and GPU boxes), `--n_samples`, `--max_new_tokens`, `--colon_token_id`,
@@ -175,7 +176,8 @@ def validate_seg(val, model, args, tokenizer):
 
 @torch.no_grad()
 def validate_vqa(val, model, args, tokenizer):
-    """-> list of new-token id lists.  One `model.generate` per sample with the reference's keyword set; answers appended to
+    """-> list of new-token id lists.  One `model.generate` per sample with the reference's keyword set (--temperature > 0: one
+    `model.generate_sample`, the sampling HF runs for do_sample=True); answers appended to
     --answers-file as JSON lines (`text` when a tokenizer can decode, the raw new ids otherwise)."""
     sink = None
     if args.answers_file:
@@ -185,10 +187,15 @@ def validate_vqa(val, model, args, tokenizer):
     for idx, batch in enumerate(val):
         batch = _staged(batch)
         input_ids, attention_mask = _prompt_part(batch, args.colon_token_id)
-        output_ids = model.generate(
-            input_ids, images=batch["images_clip"], attention_mask=attention_mask, mask_images=batch.get("mask_images", None),
-            image_token_types=batch.get("image_token_types", None), do_sample=True if args.temperature > 0 else False,
-            temperature=args.temperature, top_p=args.top_p, num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, use_cache=True)
+        common = dict(images=batch["images_clip"], attention_mask=attention_mask, mask_images=batch.get("mask_images", None),
+                      image_token_types=batch.get("image_token_types", None), num_beams=args.num_beams, max_new_tokens=args.max_new_tokens,
+                      use_cache=True)
+        if args.temperature > 0:
+            # do_sample=True in the reference: HF's warper chain temperature -> top-k -> top-p.  top_k = 50 is HF's GenerationConfig
+            # default, which the reference inherits by not passing one
+            output_ids = model.generate_sample(input_ids, temperature=args.temperature, top_k=50, top_p=args.top_p, **common)
+        else:
+            output_ids = model.generate(input_ids, do_sample=False, temperature=args.temperature, top_p=args.top_p, **common)
         new = torch.as_tensor(output_ids)[:, input_ids.shape[1]:]
         answers.append(new[0].tolist())
         if sink is not None:

@@ -12,13 +12,15 @@ a stop the mask of the first <SEG> as the sparse [row, col] list of sigmoid > 0.
 `json.dumps({"text", "mask", "height", "width", "error_code": 0}).encode() + b"\\0"` (:531-538).  Here the token loop is
 `MedPLIBForCausalLM.generate_stream`: the draw and the pick run on the device inside the captured decode step, top_p is read and ignored as in
 the reference, and every request takes its sampling seed from torch's global generator, where the reference's multinomial takes its draws
-(torch.manual_seed makes a sequence of requests repeatable).
+(torch.manual_seed makes a sequence of requests repeatable).  With --apply-top-p the request's top_p (the front end's slider) and an
+optional top_k (default 0: none) truncate the distribution before the draw — HF's top-k, then top-p, in the same captured step
+(ops.sample_rows_filtered); without the flag a request is served exactly as the reference serves it.
 
 Out of scope: the HTTP server (FastAPI / uvicorn), the controller registration, the heartbeat thread and the concurrency semaphore;
 --limit-model-concurrency is parsed and carried for a server built around `ModelWorker.generate_stream_gate`.
 
 `images` / `region_masks` of a request: base64 strings as the reference's clients send them (decoded with Pillow, which is imported only then)
-or uint8 arrays ([H, W, 3] RGB, [H, W]).  `FLAG_TABLE` holds the reference's command line as data; addition of this build: --precision."""
+or uint8 arrays ([H, W, 3] RGB, [H, W]).  `FLAG_TABLE` holds the reference's command line as data; additions of this build: --precision, --apply-top-p."""
 import argparse
 import base64
 import io
@@ -48,6 +50,7 @@ FLAG_TABLE = (
     ("add_region_feature", False, OFF), ("image_w", 336, int), ("image_h", 336, int), ("device_map", "cpu", str),
     # ---- this build's addition
     ("precision", "bf16", ("fp32", "bf16", "fp16", "int8", "int4")),
+    ("apply-top-p", False, OFF),         # honour the request's top_p (and an optional top_k); the reference reads top_p and drops it
 )
 MAX_NEW_TOKENS_CAP = 1024
 MASK_THRESHOLD = 0.1
@@ -159,7 +162,9 @@ class ModelWorker:
             raise ValueError("a request needs one image: the model's prompt carries the <image> features")
         region_masks, region_valid = self._regions(params)
         temperature = float(params.get("temperature", 1.0))
-        top_p = float(params.get("top_p", 1.0))                 # read and never used, as in the reference
+        top_p = float(params.get("top_p", 1.0))                 # read and never used, as in the reference, unless --apply-top-p
+        apply_top_p = bool(getattr(self.args, "apply_top_p", False))
+        top_k = int(params.get("top_k", 0)) if apply_top_p else 0
         max_new_tokens = min(int(params.get("max_new_tokens", 256)), MAX_NEW_TOKENS_CAP)
         stop_str = params.get("stop", None)
         stop_idx = None
@@ -179,7 +184,7 @@ class ModelWorker:
                 np.asarray([input_ids], dtype=np.int64), clip, images=sam, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,
                 stop_token_id=stop_idx, eos_token_id=tok.eos_token_id, stream_interval=self.args.stream_interval,
                 sample_seed=int(torch.randint(0, 2 ** 31 - 1, (1,))), resize_list=resize_list, original_size_list=original_size_list,
-                region_masks=region_masks, valid_region_masks_bool=region_valid, stop_check=stop_seen):
+                region_masks=region_masks, valid_region_masks_bool=region_valid, stop_check=stop_seen, top_k=top_k, apply_top_p=apply_top_p):
             text = decode(new_ids)
             if stop_str:
                 pos = text.rfind(stop_str)

@@ -1,0 +1,119 @@
+"""What top-k / top-p truncation adds to temperature sampling on the device (scripts/sample_bench.py's protocol):
+  1. microseconds per launch on a [1, 32000] fp32 row — 200 launches captured into one HIP graph and replayed — of mp_sample_rows_f32 and
+     of mp_sample_filtered_rows_f32 at (k = 50, p = 0.9), (k = 0, p = 0.9) and (k = 50, p = 1), all in the same run, the graphs replayed
+     alternately; the ratios to the plain pick;
+  2. milliseconds per token of the captured decode step with the plain pick (draw + mp_sample_rows_f32) against the filtered pick
+     (k = 50, p = 0.9), dense and MoE at bench.py's decode configuration (7B dims, batch 1, 64-token prompt): generate_stream's slope
+     between two lengths (the fastest of three calls per length after one untimed call), the two picks measured alternately in the same
+     process on the same model.
+python scripts/sample_filtered_bench.py [--new 32] [--models dense,moe] [--out profiles/sample_filtered_bench.json]"""
+import argparse
+import gc
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from medplib_amd import ops
+from medplib_amd.model.config import MedPLIBConfig
+from medplib_amd.model.medplib import LISAForCausalLM, MedPLIBForCausalLM
+
+T = 0.7
+FILTERS = {"k50_p0.9": (50, 0.9), "k0_p0.9": (0, 0.9), "k50_p1": (50, 1.0)}
+
+
+def kernel_us(dev, cols=32000, launches=200, replays=20):
+    g = torch.Generator().manual_seed(0)
+    logits = (torch.randn(1, cols, generator=g) * 2).to(dev)
+    u = torch.tensor([0.37], device=dev)
+    fns = {"sample_rows": lambda: ops.sample_rows(logits, u, T)}
+    for name, (k, p) in FILTERS.items():
+        fns["filtered_" + name] = lambda k=k, p=p: ops.sample_rows_filtered(logits, u, T, k, p)
+    graphs = {}
+    for name, fn in fns.items():
+        fn(); torch.cuda.synchronize()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(graphs[name], stream=side):
+                for _ in range(launches):
+                    fn()
+        torch.cuda.current_stream().wait_stream(side)
+        graphs[name].replay(); torch.cuda.synchronize()
+    best = {name: float("inf") for name in fns}
+    for _ in range(replays):
+        for name, graph in graphs.items():                # alternately: a drift of the box hits every kernel alike
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); graph.replay(); b.record(); torch.cuda.synchronize()
+            best[name] = min(best[name], a.elapsed_time(b))
+    out = {name: round(ms * 1e3 / launches, 3) for name, ms in best.items()}
+    for name in FILTERS:
+        out[f"filtered_{name}_over_sample_rows"] = round(out["filtered_" + name] / out["sample_rows"], 3)
+    kept = {name: int(ops.sample_rows_filtered(logits, u, T, k, p, want_cut=True)[1][0]) for name, (k, p) in FILTERS.items()}
+    out["kept_columns"] = kept
+    return out
+
+
+def step_ms(model, dev, new):
+    cfg = model.config
+    g = torch.Generator().manual_seed(0)
+    L, V = 64, cfg.vocab_size
+    ids = torch.randint(3, 31999, (1, L), generator=g)
+    ids[0, 0] = 1; ids[0, 34], ids[0, 35], ids[0, 36] = V - 2, -200, V - 1
+    clip = torch.randn(1, 3, 336, 336, generator=g).to(torch.bfloat16).to(dev)
+
+    def run(kw, n_new):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in model.generate_stream(ids.numpy(), clip, temperature=T, max_new_tokens=n_new, eos_token_id=-1, stream_interval=16, **kw):
+            pass
+        torch.cuda.synchronize()
+        assert model.last_decode_path == "graph"
+        return time.perf_counter() - t0
+
+    picks = {"plain": {}, "filtered": dict(top_k=50, top_p=0.9, apply_top_p=True)}
+    for kw in picks.values():
+        run(kw, 8)
+    best = {(k, n): float("inf") for k in picks for n in (new, 4 * new)}
+    for _ in range(3):
+        for n_new in (new, 4 * new):
+            for k, kw in picks.items():                  # alternately: a drift of the box hits both picks alike
+                best[(k, n_new)] = min(best[(k, n_new)], run(kw, n_new))
+    res = {k: round((best[(k, 4 * new)] - best[(k, new)]) / (3 * new) * 1e3, 4) for k in picks}
+    res["filtered_over_plain"] = round(res["filtered"] / res["plain"], 4)
+    res["filtered_minus_plain_us"] = round((res["filtered"] - res["plain"]) * 1e3, 1)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--new", type=int, default=32)
+    ap.add_argument("--models", default="dense,moe")
+    ap.add_argument("--out", default=None, help="also write the JSON result to this file")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    out = {"script": "python scripts/sample_filtered_bench.py --new %d --models %s" % (args.new, args.models),
+           "temperature": T,
+           "kernel_us_per_launch_1x32000": kernel_us(dev),
+           "metric": "decode ms/token (generate_stream, captured graph, batch 1, KV cache, 7B dims, stream_interval 16); filtered: top_k 50, top_p 0.9",
+           "new_tokens": [args.new, 4 * args.new]}
+    print(json.dumps(out["kernel_us_per_launch_1x32000"]), flush=True)
+    for name, cls, moe in (("dense", LISAForCausalLM, False), ("moe", MedPLIBForCausalLM, True)):
+        if name not in args.models.split(","):
+            continue
+        model = cls(MedPLIBConfig.medplib_7b(moe_enable=moe), device=dev).eval()
+        out[name] = step_ms(model, dev, args.new)
+        print(name, json.dumps(out[name]), flush=True)
+        model = None
+        gc.collect(); torch.cuda.empty_cache()
+    line = json.dumps(out, indent=1)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
