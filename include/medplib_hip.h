@@ -139,6 +139,7 @@ int mp_gemv_rmsnorm_rope_append_bf16(const void* x, int64_t ldx, const float* no
 /* Bit flags of the sticky int32 error word the bounded decode entry points OR into (never cleared by the library). */
 #define MP_POS_ERR_TABLE 1   /* *pos_dev outside [0, table_rows): no RoPE row */
 #define MP_POS_ERR_CACHE 2   /* *pos_dev outside [0, cache_rows): no KV-cache row */
+#define MP_POS_ERR_BEAM 4    /* beam search: a parent outside [0, nb), or fewer than 2 * nb candidates */
 /* mp_gemv_rmsnorm_rope_append_bf16 bounded on the device: table_rows = rows of cos_t / sin_t, cache_rows = max_len of the caches, err = an
  * int32 error word in device memory.  When *pos_dev is outside [0, table_rows) or [0, cache_rows) the launch reads no table row and writes
  * nothing (neither q nor the caches) and ORs MP_POS_ERR_TABLE / MP_POS_ERR_CACHE into *err; it does not trap.  In range: the bits of the
@@ -227,6 +228,38 @@ int mp_sample_rows_f32(const float* logits, int64_t ld, int64_t rows, int cols, 
 int mp_sample_filtered_rows_f32(const float* logits, int64_t ld, int64_t rows, int cols, float inv_temperature, int top_k, float top_p,
                                 const float* u, int64_t* out, int* kept /* nullable [rows] */, float* cut /* nullable [rows] */,
                                 hipStream_t stream);
+/* One step of beam search over the nb beams' next-token logits (HF 4.31 GenerationMixin.beam_search + BeamSearchScorer.process; what the
+ * reference's vqa_infer.py:430-442 asks of generate(num_beams=nb, do_sample=False)).  logits fp32 [nb, cols] with row stride ld; ld = 0: every
+ * beam reads the same row (the first step, fed from the prefill's single row).
+ *   value: v(b, c) = ((l - m_b) - log sum_c' exp(l_c' - m_b)) + beam_scores[b], m_b the row maximum: HF's log_softmax(logits.float()) +
+ *     beam_scores[:, None] in fp32, the sum in one fixed order.  NaN columns are left out of the maximum and the sum and are never
+ *     candidates; a row whose maximum is not finite has none.  -inf columns are candidates with value -inf.
+ *   ranking: cand_score / cand_index [2 * nb] = the 2 * nb largest v over the nb x cols candidates, sorted by value descending, then by flat
+ *     index b * cols + c ascending (a stated tie rule; torch.topk's is not).  Fewer than 2 * nb candidates: the unfilled entries get index -1
+ *     and score -inf, and MP_POS_ERR_BEAM is ORed into *err.
+ *   selection: walking the candidates in rank order, those whose token c is eos_id are skipped (eos_id = -1: none is) and the first nb of the
+ *     rest become next_scores / next_tokens (c) / next_parent (b) [nb].  One eos id gives at most nb eos candidates, so nb others exist
+ *     among 2 * nb filled ones; continuations that cannot be filled get score -inf, token 0, parent 0.  next_scores may alias beam_scores.
+ * Two launches (one block per beam, then one wave that merges), no float atomics, no host read, no allocation: capturable, and every output
+ * has the same bits for the same inputs on every launch, alone or in a graph.  The rows' candidates pass between the launches through one
+ * buffer per device: calls on different streams of one device must not overlap.
+ * 1 <= nb <= 8, 2 <= cols <= 65536, ld >= cols or ld == 0, else MP_ERR_SHAPE; a null operand MP_ERR_ARG; both before any launch. */
+int mp_beam_topk_f32(const float* logits, int64_t ld, int nb, int cols, const float* beam_scores, int eos_id,
+                     float* cand_score, int* cand_index,                       /* [2*nb] each */
+                     float* next_scores, int64_t* next_tokens, int* next_parent, /* [nb] each */
+                     int* err, hipStream_t stream);
+/* HF's _reorder_cache for the beams of one prompt, in place, over the generated tail only: tensors = a device table of n base pointers (each
+ * layer's K and V, bf16 [nb, cache_rows, row_elems] with batch_stride elements between beams); for every tensor and every position p with
+ * lo <= p < min(*hi_dev, cache_rows): new[b, p] = old[parent[b], p].  The prompt positions (< lo) are equal in every beam and never move.
+ * A thread owns one 16-byte slice of one (tensor, position) across all beams, loads the nb slices and stores the ones that move: no hazard.
+ * An identity parent stores nothing.  The grid is fixed by (n, cache_rows - lo, row_elems) and the bound is read on the device, so the launch
+ * can sit in a captured graph.  A parent entry outside [0, nb) writes nothing anywhere and ORs MP_POS_ERR_BEAM into *err; a null table entry
+ * or one off 16 bytes leaves that tensor alone and sets the same bit.
+ * 0 <= n <= 65535, 1 <= nb <= 8, row_elems a positive multiple of 8, cache_rows > 0, lo >= 0, batch_stride a multiple of 8 and
+ * >= cache_rows * row_elems, else MP_ERR_SHAPE; a null operand (n > 0) MP_ERR_ARG; both before any launch.  n == 0: nothing launched. */
+int mp_kv_permute_rows_bf16(const void* tensors /* device table of n base pointers */, int n, const int* parent, int nb,
+                            int64_t batch_stride, int64_t row_elems, int lo, const int* hi_dev, int cache_rows,
+                            int* err, hipStream_t stream);
 /* out = silu(gu[:, :ff]) * gu[:, ff:]  (LlamaMLP). */
 int mp_swiglu_bf16(const void* gu, int64_t ldgu, void* out, int64_t ldo, int64_t rows, int ff, hipStream_t stream);
 int mp_cast_f32_to_bf16(const float* x, void* y, int64_t n, hipStream_t stream);

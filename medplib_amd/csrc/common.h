@@ -17,6 +17,7 @@
 // bits the bounded decode RoPE / KV-append kernels OR into their sticky device error word (include/medplib_hip.h)
 #define MP_POS_ERR_TABLE 1         // position outside [0, table_rows): no RoPE row to read
 #define MP_POS_ERR_CACHE 2         // position outside [0, cache_rows): no KV-cache row to write
+#define MP_POS_ERR_BEAM 4          // beam search: a parent outside [0, nb), or fewer than 2 * nb candidates
 #define MP_POS_UNBOUNDED 0x7fffffff   // table_rows / cache_rows of the unbounded entry points
 
 typedef __bf16 bf16_t;

@@ -53,6 +53,12 @@ def _np_ids(t):
     return t.detach().cpu().numpy()
 
 
+# HF generate kwargs the entry points accept when they mean what the entry point does (the reference driver's set, vqa_infer.py:430-442)
+_GENERATE_KWARGS = frozenset({"do_sample", "temperature", "top_p", "num_beams", "use_cache", "mask_images", "image_token_types",
+                              "image_token_lengths", "region_masks", "valid_region_masks_bool", "output_hidden_states",
+                              "return_dict_in_generate", "pad_token_id"})
+
+
 def _argmax_pick(logits, step):
     """The greedy next-token pick (HF do_sample=False).  `step` (the number of the generated token) is not used."""
     return ops.argmax_rows(logits)
@@ -931,16 +937,16 @@ class MedPLIBForCausalLM(nn.Module):
             raise NotImplementedError("generate(): sampling (do_sample / temperature > 0) is not built here: call generate_sample() "
                                       "(temperature, top-k, top-p); the shipped eval scripts decode greedily")
         if (kwargs.get("num_beams") or 1) != 1:
-            raise NotImplementedError("generate(): beam search (num_beams > 1) is not built; the shipped eval scripts use num_beams=1")
-        unknown = set(kwargs) - {"do_sample", "temperature", "top_p", "num_beams", "use_cache", "mask_images", "image_token_types",
-                                 "image_token_lengths", "region_masks", "valid_region_masks_bool", "output_hidden_states",
-                                 "return_dict_in_generate", "pad_token_id"}
+            raise NotImplementedError("generate(): beam search (num_beams > 1) is not built here: call generate_beam(); the shipped eval "
+                                      "scripts use num_beams=1")
+        unknown = set(kwargs) - _GENERATE_KWARGS
         if unknown:
             raise TypeError(f"generate(): unsupported arguments {sorted(unknown)}")
         return self._generate_rows("generate", input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs, lambda b: _argmax_pick)
 
-    def _generate_rows(self, who, input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs, pick_of_row):
-        """generate() / generate_sample(): batch rows decoded one after the other, row b's next token chosen by pick_of_row(b); output ids
+    def _generate_rows(self, who, input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs, pick_of_row, decode_row=None):
+        """generate() / generate_sample() / generate_beam(): batch rows decoded one after the other, row b's next token chosen by
+        pick_of_row(b) — or the whole row decoded by decode_row(row ids, images, region masks, their flags) -> ids [1, L + n]; output ids
         [B, L + n_max], prompt included, right-padded with eos."""
         self._require_shadowable(who)
         self.sync_side_streams()
@@ -960,8 +966,11 @@ class MedPLIBForCausalLM(nn.Module):
                 if len(rm) > 0:            # the collator's flat list holds one entry per sample WITH regions: pick this row's
                     before = sum(1 for v in rv[:b] if any(v))
                     rm, rv = (rm[before:before + 1] if any(rv[b]) else ()), rv[b:b + 1]
-                out, _ = self._greedy(row, img, max_new_tokens, eos_token_id, kwargs.get("mask_images"), kwargs.get("image_token_types"),
-                                      kwargs.get("image_token_lengths"), rm, rv, pick=pick_of_row(b))
+                if decode_row is not None:
+                    out = decode_row(row, img, rm, rv)
+                else:
+                    out, _ = self._greedy(row, img, max_new_tokens, eos_token_id, kwargs.get("mask_images"), kwargs.get("image_token_types"),
+                                          kwargs.get("image_token_lengths"), rm, rv, pick=pick_of_row(b))
                 rows.append(out[0])
         self.train(was_training)
         n = max(r.shape[0] for r in rows)
@@ -991,6 +1000,169 @@ class MedPLIBForCausalLM(nn.Module):
         top_k, top_p = int(top_k or 0), 1.0 if top_p is None else float(top_p)
         return self._generate_rows("generate_sample", input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs,
                                    lambda b: _SamplePick(temperature, seed + b, self.device_, top_k=top_k, top_p=top_p))
+
+    @torch.no_grad()
+    def generate_beam(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, num_beams=4, length_penalty=1.0,
+                      early_stopping=False, debug=None, **kwargs):
+        """generate() with HF 4.31's beam search (GenerationMixin.beam_search + BeamSearchScorer; what vqa_infer.py:430-442 asks for with
+        --num_beams > 1): generate(num_beams=, do_sample=False, num_return_sequences=1, length_penalty=, early_stopping=False | True), one
+        sample at a time.  The num_beams beams of a prompt are the rows of one decode step: they share the position counter and one pass over
+        the weights.  Between two steps the device ranks the candidates (ops.beam_topk) and re-orders the generated tail of the KV cache by
+        the chosen parents (ops.kv_permute_rows); the hypotheses live on the host (medplib_amd.beam.BeamScorer, replayed over the recorded
+        candidates at every look).  Decode path (last_decode_path): the captured graph under generate()'s conditions, else a token-by-token
+        loop that re-orders the whole cache with index_select.  Same return layout as generate(): prompt included, right-padded with eos; an
+        answer that ended on eos carries it when it fits, as HF's finalize writes it.  last_beam_scores: the winner's score per row.
+        Refused: do_sample=True (beam sampling), num_return_sequences != 1, early_stopping="never", num_beams > 8.
+        debug: a list that receives one dict per kept step — the fp32 logits [num_beams, V] on the host, the input beam scores, the candidates
+        and the selection (tests; costs a sync per token)."""
+        if kwargs.get("do_sample") or (kwargs.get("temperature") or 0) > 0 and kwargs.get("do_sample") is not False:
+            raise NotImplementedError("generate_beam(): beam sampling (do_sample / temperature > 0 with num_beams > 1) is not built")
+        if (kwargs.get("num_return_sequences") or 1) != 1:
+            raise NotImplementedError("generate_beam(): num_return_sequences != 1 is not built: the best beam is returned")
+        if early_stopping not in (False, True):
+            raise NotImplementedError(f"generate_beam(): early_stopping={early_stopping!r} is not built (False or True)")
+        nb = int(num_beams)
+        if not 1 <= nb <= 8:
+            raise NotImplementedError(f"generate_beam(): num_beams={num_beams} is not built: 1 to 8 beams share one decode step")
+        unknown = set(kwargs) - _GENERATE_KWARGS - {"num_return_sequences"}
+        if unknown:
+            raise TypeError(f"generate_beam(): unsupported arguments {sorted(unknown)}")
+        max_new_tokens = int(max_new_tokens)
+        assert max_new_tokens >= 1
+        self.last_beam_scores = []
+
+        def decode_row(row, img, rm, rv):
+            new, score = self._beam_row(row, img, max_new_tokens, int(eos_token_id), nb, float(length_penalty), bool(early_stopping),
+                                        kwargs.get("mask_images"), kwargs.get("image_token_types"), kwargs.get("image_token_lengths"), rm, rv, debug)
+            self.last_beam_scores.append(score)
+            return np.concatenate([row, np.asarray(new, dtype=np.int64)[None]], 1)
+
+        return self._generate_rows("generate_beam", input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs, None, decode_row)
+
+    def _beam_row(self, ids, images_clip, max_new_tokens, eos_token_id, nb, length_penalty, early_stopping, mask_images, image_token_types,
+                  image_token_lengths, region_masks, valid_region_masks_bool, debug, check_every=16):
+        """Beam search on one sample -> (generated ids of the winning hypothesis, its score).  Prefill at batch 1 — the launches of _decode —
+        into row 0 of a cache of nb rows, the prompt's K/V copied to the other rows; then one decode step per token at B = nb.  The step's
+        record (cand_score | cand_index | next_scores | next_parent | next_tokens, one buffer) is the state the next step reads and is copied
+        to a history row after every step; BeamScorer replays the history on the host."""
+        from ..beam import BeamScorer
+        cfg, dev, m = self.config, self.device_, self.model
+        llm, d = m.llm, cfg.hidden_size
+        plan, feats = self._encode_and_plan(ids, None, None, images_clip, mask_images, image_token_types, image_token_lengths,
+                                            with_seg=False, region_masks=region_masks if region_masks else None,
+                                            valid_region_masks_bool=valid_region_masks_bool)
+        src = _h2d(plan.src_code.reshape(-1), dev)
+        S = plan.seq_len
+        embeds = ops.splice_rows(llm.embed_tokens, feats, src, d).view(1, S, d)
+        cache = llm.new_kv_cache(nb, S + max_new_tokens)
+        row0 = {"len": 0, "k": [t[:1] for t in cache["k"]], "v": [t[:1] for t in cache["v"]], "err": cache["err"]}
+        hidden, _, _ = llm.forward(embeds, None, kv_cache=row0)
+        cache["len"] = S
+        if nb > 1:
+            for t in cache["k"] + cache["v"]:
+                t[1:, :S].copy_(t[:1, :S])
+        # the step record: one buffer, so that one copy files a step
+        rec = torch.zeros(32 * nb, dtype=torch.uint8, device=dev)
+        cs, ci = rec[:8 * nb].view(torch.float32), rec[8 * nb:16 * nb].view(torch.int32)
+        ns, par, tok = rec[16 * nb:20 * nb].view(torch.float32), rec[20 * nb:24 * nb].view(torch.int32), rec[24 * nb:].view(torch.int64)
+        hist = torch.empty((max_new_tokens, 32 * nb), dtype=torch.uint8, device=dev)
+        first_scores = [0.0] + [-1e9] * (nb - 1)                  # HF's beam_scores[:, 1:] = -1e9: the first step ranks one row
+        ns.copy_(torch.tensor(first_scores, dtype=torch.float32))
+        scorer = BeamScorer(nb, length_penalty, early_stopping, eos_token_id, length_base=ids.shape[1], max_new_tokens=max_new_tokens)
+        n_dbg = len(debug) if debug is not None else 0
+        scores_in = [torch.tensor(first_scores, dtype=torch.float32)]
+
+        def unpack(row):
+            """A history row on the host -> (cand_score, cand_index, next_scores, next_parent, next_tokens)."""
+            return (row[:8 * nb].view(np.float32), row[8 * nb:16 * nb].view(np.int32), row[16 * nb:20 * nb].view(np.float32),
+                    row[20 * nb:24 * nb].view(np.int32), row[24 * nb:].view(np.int64))
+
+        def note(logits):                    # debug (tests): this step's logits, input scores, candidates and selection, read back at once
+            c_s, c_i, n_s, n_p, n_t = unpack(rec.cpu().numpy())
+            debug.append({"logits": logits.float().cpu().expand(nb, -1), "scores_in": scores_in[0], "cand_score": c_s, "cand_index": c_i,
+                          "next_scores": n_s, "next_parent": n_p, "next_tokens": n_t})
+            scores_in[0] = torch.from_numpy(n_s.copy())
+
+        def feed(rows, err):
+            """The scorer over recorded steps, until done -> done."""
+            if err:
+                raise RuntimeError(f"_beam_row: a decode step ran past the RoPE table ({llm.cos.shape[0]} rows) or the KV cache "
+                                   f"({cache['k'][0].shape[1]} rows), or the beam selection ran out of candidates (NaN logits): error word {err}")
+            V = cfg.vocab_size
+            for row in rows:
+                c_s, c_i, _, _, _ = unpack(row)
+                if scorer.step([(float(s), int(i) // V, int(i) % V) for s, i in zip(c_s, c_i)]):
+                    return True
+            return False
+
+        def step_out(logits, shared=False):
+            ops.beam_topk(logits, ns, eos_token_id, cs, ci, ns, tok, par, cache["err"], nb=nb if shared else None)
+
+        logits = llm.next_token_logits(hidden[0, -1:])
+        assert logits.shape[1] == cfg.vocab_size
+        step_out(logits, shared=True)
+        hist[0].copy_(rec)
+        if debug is not None:
+            note(logits)
+        pass0 = llm.gate_pass
+        try:
+            if self.decode_with_graph and max_new_tokens > 2 and self._graph_decode_ok():
+                self.last_decode_path = "graph"
+                counters = torch.tensor([S, S + 1], dtype=torch.int32, device=dev)
+                pass_dev = torch.tensor([pass0 + 1], dtype=torch.int32, device=dev)
+                table, kept_alive = ops.kv_permute_table(cache)
+                static = {}
+
+                def step():
+                    ops.kv_permute_rows(table, cache["k"][0], par, S, counters[0:1], cache["err"])     # the tail follows the chosen parents
+                    emb = ops.splice_rows(llm.embed_tokens, None, tok, d)
+                    h = llm.decode_step(emb.view(nb, 1, d), cache, counters, pass_dev=pass_dev)
+                    static["logits"] = llm.next_token_logits(h.view(nb, d))
+                    step_out(static["logits"])
+                    ops.advance_ints(counters, 1)
+                    ops.advance_ints(pass_dev, 1)
+
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(torch.cuda.current_stream())
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.stream(side):
+                    with torch.cuda.graph(graph, stream=side):
+                        step()
+                torch.cuda.current_stream().wait_stream(side)
+                n = 1
+                for upto in list(range(1 + check_every, max_new_tokens, check_every)) + [max_new_tokens]:
+                    for i in range(n, upto):
+                        graph.replay()                               # feeds the tokens of step i-1, records step i
+                        hist[i].copy_(rec)
+                        if debug is not None:
+                            note(static["logits"])
+                    # the only host synchronisation of the loop: the steps' records and the cache's error word in one copy
+                    got = torch.cat([hist[scorer.steps:upto].reshape(-1), cache["err"].view(torch.uint8)]).cpu().numpy()
+                    n = upto
+                    if feed(got[:-4].reshape(-1, 32 * nb), int(got[-4:].view(np.int32)[0])):
+                        break
+            else:
+                self.last_decode_path = "loop"
+                for i in range(max_new_tokens):
+                    if feed(hist[i:i + 1].cpu().numpy(), int(cache["err"][0])) or i == max_new_tokens - 1:
+                        break
+                    if nb > 1:                                       # HF's _reorder_cache: the whole cache, by the chosen parents
+                        sel = par.to(torch.int64)
+                        cache["k"] = [t.index_select(0, sel) for t in cache["k"]]
+                        cache["v"] = [t.index_select(0, sel) for t in cache["v"]]
+                    emb = ops.splice_rows(llm.embed_tokens, None, tok.clone(), d)
+                    h, _, _ = llm.forward(emb.view(nb, 1, d), None, kv_cache=cache)
+                    logits = llm.next_token_logits(h.view(nb, d))
+                    step_out(logits)
+                    hist[i + 1].copy_(rec)
+                    if debug is not None:
+                        note(logits)
+        finally:
+            llm.gate_pass = pass0 + max(scorer.steps, 1) - 1        # the passes of the kept steps (replays past `done` are discarded)
+            llm._draws_key = None                                    # (a captured draw buffer belongs to its graph)
+            if debug is not None:
+                del debug[n_dbg + scorer.steps:]
+        return scorer.finalize()
 
     @torch.no_grad()
     def generate_stream(self, input_ids, images_clip, images=None, temperature=1.0, top_p=1.0, max_new_tokens=256, stop_token_id=None,

@@ -944,6 +944,52 @@ def sample_uniform_dev(seed, step_dev, device):
     return gate_noise_dev(1, seed, step_dev, 1, False, device)
 
 
+POS_ERR_BEAM = 4          # MP_POS_ERR_BEAM: a parent outside [0, nb), or fewer than 2 * nb candidates
+
+
+def beam_topk(logits, beam_scores, eos_id, cand_score, cand_index, next_scores, next_tokens, next_parent, err, nb=None):
+    """One beam-search step (mp_beam_topk_f32): the 2 * nb best of log_softmax(logits) + beam_scores[:, None] by (value descending, flat index
+    b * cols + c ascending) into cand_score fp32 / cand_index int32 [2 * nb], and the first nb of them whose token is not eos_id into
+    next_scores fp32 / next_tokens int64 / next_parent int32 [nb].  logits fp32 [nb, cols], or [1, cols] with nb given: every beam reads that
+    row (the first step).  next_scores may be beam_scores.  Fewer than 2 * nb candidates: POS_ERR_BEAM in err (int32 [1])."""
+    _chk(logits, torch.float32, "beam_topk.logits"); _chk(beam_scores, torch.float32, "beam_topk.beam_scores")
+    _chk(cand_score, torch.float32, "beam_topk.cand_score"); _chk(cand_index, torch.int32, "beam_topk.cand_index")
+    _chk(next_scores, torch.float32, "beam_topk.next_scores"); _chk(next_tokens, torch.int64, "beam_topk.next_tokens")
+    _chk(next_parent, torch.int32, "beam_topk.next_parent"); _chk(err, torch.int32, "beam_topk.err")
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    shared = nb is not None and logits.shape[0] == 1
+    nb = logits.shape[0] if nb is None else int(nb)
+    assert shared or logits.shape[0] == nb, "beam_topk: logits [nb, cols], or one row with nb given"
+    for t_, n_ in ((beam_scores, nb), (cand_score, 2 * nb), (cand_index, 2 * nb), (next_scores, nb), (next_tokens, nb), (next_parent, nb)):
+        assert t_.dim() == 1 and t_.is_contiguous() and t_.numel() == n_
+    lib().call("mp_beam_topk_f32", _p(logits), 0 if shared else logits.stride(0), nb, logits.shape[1], _p(beam_scores), int(eos_id), _p(cand_score),
+               _p(cand_index), _p(next_scores), _p(next_tokens), _p(next_parent), _p(err), _stream())
+
+
+def kv_permute_table(cache):
+    """The device table of base pointers kv_permute_rows takes, for a KV cache of LlamaStack.new_kv_cache (or a list of equally shaped bf16
+    tensors [nb, rows, ...]): every layer's K, then every layer's V.  -> (int64 [n] on the device, the tensors: keep them alive)."""
+    tensors = list(cache["k"]) + list(cache["v"]) if isinstance(cache, dict) else list(cache)
+    first = tensors[0]
+    for t_ in tensors:
+        _chk(t_, torch.bfloat16, "kv_permute_table")
+        assert t_.shape == first.shape and t_.stride() == first.stride() and t_[0].is_contiguous() and t_.data_ptr() % 16 == 0
+    return torch.tensor([t_.data_ptr() for t_ in tensors], dtype=torch.int64).to(first.device), tensors
+
+
+def kv_permute_rows(table, like, parent, lo, hi_dev, err):
+    """In place, for every tensor of a kv_permute_table and every position lo <= p < min(hi_dev[0], rows): t[b, p] = t[parent[b], p]
+    (mp_kv_permute_rows_bf16: HF's _reorder_cache over the generated tail only).  like: one of the table's tensors [nb, rows, ...] (the shape
+    and strides of all); parent int32 [nb], hi_dev int32 [1] and err int32 [1] on the device.  A parent outside [0, nb): nothing is written,
+    POS_ERR_BEAM in err."""
+    _chk(table, torch.int64, "kv_permute_rows.table"); _chk(like, torch.bfloat16, "kv_permute_rows.like")
+    _chk(parent, torch.int32, "kv_permute_rows.parent"); _chk(hi_dev, torch.int32, "kv_permute_rows.hi_dev"); _chk(err, torch.int32, "kv_permute_rows.err")
+    nb, rows = like.shape[0], like.shape[1]
+    assert table.dim() == 1 and table.is_contiguous() and parent.is_contiguous() and parent.numel() == nb and like[0].is_contiguous()
+    lib().call("mp_kv_permute_rows_bf16", _p(table), table.numel(), _p(parent), nb, like.stride(0) if nb > 1 else like[0].numel(),
+               like[0, 0].numel(), int(lo), _p(hi_dev), rows, _p(err), _stream())
+
+
 def swiglu_interleave(gate, up):
     """Pack gate/up projection weights [ff, d] into the row order the SWIGLU_PAIR epilogue expects: blocks of 32 gate rows
     followed by the 32 matching up rows.  (Pure data movement.)"""

@@ -177,7 +177,7 @@ def validate_seg(val, model, args, tokenizer):
 @torch.no_grad()
 def validate_vqa(val, model, args, tokenizer):
     """-> list of new-token id lists.  One `model.generate` per sample with the reference's keyword set (--temperature > 0: one
-    `model.generate_sample`, the sampling HF runs for do_sample=True); answers appended to
+    `model.generate_sample`, the sampling HF runs for do_sample=True; --num_beams > 1 without it: one `model.generate_beam`); answers appended to
     --answers-file as JSON lines (`text` when a tokenizer can decode, the raw new ids otherwise)."""
     sink = None
     if args.answers_file:
@@ -194,6 +194,9 @@ def validate_vqa(val, model, args, tokenizer):
             # do_sample=True in the reference: HF's warper chain temperature -> top-k -> top-p.  top_k = 50 is HF's GenerationConfig
             # default, which the reference inherits by not passing one
             output_ids = model.generate_sample(input_ids, temperature=args.temperature, top_k=50, top_p=args.top_p, **common)
+        elif args.num_beams > 1:
+            # num_beams > 1 without sampling in the reference: HF's beam search with its defaults (length_penalty 1.0, early_stopping False)
+            output_ids = model.generate_beam(input_ids, do_sample=False, temperature=args.temperature, top_p=args.top_p, **common)
         else:
             output_ids = model.generate(input_ids, do_sample=False, temperature=args.temperature, top_p=args.top_p, **common)
         new = torch.as_tensor(output_ids)[:, input_ids.shape[1]:]
