@@ -72,7 +72,7 @@ class LlamaStack:
         self.layer_events = None           # a torch.cuda.Event per layer: model_forward creates them (gate_towers) for the towers, _mlp_gather_scatter records
         self.folded_layers = 0             # layers the last forward ran with folded norms: forward writes, bench.py / oracle/parity.py / tests read
         self.last_gate_inputs = None       # per MoE layer, the stream before the post-attention norm: forward(collect_routing=True) writes, oracle/parity.py reads
-        self._draws_key = None             # what _draws_all was drawn for: _gate_draws writes and reads; medplib._decode_graph and tests reset it to None
+        self._draws_key = None             # what _draws_all was drawn for: _gate_draws writes and reads; generation._captured_steps and tests reset it to None
         self._draws_all = None             # fp32 [L * T * E] gate draws of one pass, all layers: _gate_draws writes and slices
         self.fuse_moe_gather_scatter = True   # top-1, one rank: dispatch / combine folded into the expert GEMMs
         self.fuse_decode_routing = True       # decode rows: post-attention norm + gate + routing in one launch
@@ -339,7 +339,7 @@ class LlamaStack:
     def new_kv_cache(self, batch, max_len):
         """KV cache for `evaluate()`'s greedy decode (HF `use_cache=True`, MedPLIB.py:592-606): post-RoPE K and V per layer, and "err", the
         int32 word the bounded decode kernels set (MP_POS_ERR_*) when a step's position has no table or cache row.  The RoPE tables are
-        grown to max_len HERE, before _decode_graph captures their pointers (growing after the capture would leave the graph reading the
+        grown to max_len HERE, before generation._captured_steps captures their pointers (growing after the capture would leave the graph reading the
         freed tables)."""
         cfg = self.cfg
         self.ensure_positions(max_len)

@@ -8,7 +8,10 @@ per-sample splice loop, per-mask decoder loop) is replaced by batched kernels.
 
 Dead work the reference performs but never consumes is not executed (results are identical — row-wise ops):
 full-vocabulary fp32 logits for unsupervised rows, text_hidden_fcs on non-<SEG> rows, the 32 intermediate hidden
-states, CLIP's last layer, mask tokens 1-3."""
+states, CLIP's last layer, mask tokens 1-3.
+
+Here: construction, loading, the training forward, the mask tail and `_seg_mask`.  The decode entry points (evaluate / generate / generate_sample /
+generate_beam / generate_stream) are `generation.GenerationMixin`."""
 import contextlib
 import math
 import os
@@ -24,6 +27,7 @@ from .. import ops
 from . import autograd_ops as A
 from .clip import ClipTower
 from .config import MedPLIBConfig
+from .generation import GenerationMixin, _h2d, _np_ids
 from .llama import LlamaStack
 from .sam import MaskDecoder, PromptEncoderText, SamImageEncoder
 from .icl import MaskTokenEncoder, TokenCompressor
@@ -36,60 +40,6 @@ LOSS_KEYS = ["loss", "ce_loss", "mask_bce_loss", "mask_dice_loss", "mask_loss", 
 _PRUNE_LAST_MLP = os.environ.get("MP_PRUNE_LAST_MLP", "1") != "0"
 _GATE_MODE = int(os.environ.get("MP_GATE_TOWERS", "0"))                  # 0 off, 1 gate, 2 = record the events only (A/B of the records' own cost)
 _GATE_TOWERS = _GATE_MODE >= 1              # A/B: towers that run ahead gate their layers on the previous step's decoder layers (model_forward)
-
-
-def _h2d(arr, device):
-    """Host index array -> device tensor without stalling the host: a pageable-memory copy is synchronous for the caller AND
-    ordered behind everything already queued on the stream, so one such copy after the LLM launches makes the host wait for the
-    whole stack (measured: 66 of 97 ms per step spent blocked in .to()).  Pinned staging + non_blocking lets the host run ahead and
-    queue the SAM encoder / mask tail while the LLM is still executing."""
-    t = torch.from_numpy(np.ascontiguousarray(arr))
-    return t.pin_memory().to(device, non_blocking=True)
-
-
-def _np_ids(t):
-    if isinstance(t, np.ndarray):
-        return t
-    return t.detach().cpu().numpy()
-
-
-# HF generate kwargs the entry points accept when they mean what the entry point does (the reference driver's set, vqa_infer.py:430-442)
-_GENERATE_KWARGS = frozenset({"do_sample", "temperature", "top_p", "num_beams", "use_cache", "mask_images", "image_token_types",
-                              "image_token_lengths", "region_masks", "valid_region_masks_bool", "output_hidden_states",
-                              "return_dict_in_generate", "pad_token_id"})
-
-
-def _argmax_pick(logits, step):
-    """The greedy next-token pick (HF do_sample=False).  `step` (the number of the generated token) is not used."""
-    return ops.argmax_rows(logits)
-
-
-class _SamplePick:
-    """The sampling next-token pick of generate_stream: token `step` of a request is ops.sample_rows at the uniform the keyed generator
-    draws under (seed, step).  `step` is an int (the first token, the token-by-token loop) or an int32 [1] device counter (the captured
-    decode step: every replay draws what the loop draws for that token).  An injected `uniforms(step) -> float` replaces the generator; it
-    runs on the host, so it cannot be captured.  last_u: the [1] tensor of the latest draw (inside a captured step: the graph's own buffer).
-    top_k / top_p truncate the distribution first (ops.sample_rows_filtered: HF's top-k, then top-p); with both off (0 and 1.0) the pick is
-    ops.sample_rows as before.  Temperature, top_k and top_p are launch constants of a captured step."""
-    needs_step = True                        # the captured step keeps the number of the generated token on the device
-
-    def __init__(self, temperature, seed, device, uniforms=None, top_k=0, top_p=1.0):
-        self.temperature, self.seed, self.device, self.uniforms, self.last_u = float(temperature), int(seed), device, uniforms, None
-        self.top_k, self.top_p = int(top_k), float(top_p)
-        if self.top_k < 0 or not 0.0 <= self.top_p <= 1.0:
-            raise ValueError(f"sampling: top_k={top_k} must not be negative and top_p={top_p} must lie in [0, 1]")
-
-    def __call__(self, logits, step):
-        if self.uniforms is not None:
-            u = torch.tensor([float(self.uniforms(int(step)))], dtype=torch.float32, device=self.device)
-        elif torch.is_tensor(step):
-            u = ops.sample_uniform_dev(self.seed, step, self.device)
-        else:
-            u = ops.sample_uniform(self.seed, int(step), self.device)
-        self.last_u = u
-        if self.top_k == 0 and self.top_p >= 1.0:
-            return ops.sample_rows(logits, u, self.temperature)
-        return ops.sample_rows_filtered(logits, u, self.temperature, self.top_k, self.top_p)
 
 
 class _VisualModel(nn.Module):
@@ -161,7 +111,7 @@ class StreamOrderedLosses(collections.abc.Mapping):
         return f"StreamOrderedLosses({list(self._values)})"
 
 
-class MedPLIBForCausalLM(nn.Module):
+class MedPLIBForCausalLM(GenerationMixin, nn.Module):
     moe_default = True
 
     def __init__(self, config: Optional[MedPLIBConfig] = None, device="cuda", **kwargs):
@@ -782,454 +732,6 @@ class MedPLIBForCausalLM(nn.Module):
             out10 = A.MaskLossFn.apply(pred_flat, gt_flat, iou_pred, ce, weights, offsets)
         return {k: out10[i] for i, k in enumerate(LOSS_KEYS)}
 
-
-    def _decode_graph(self, prefill_hidden, cache, S, max_new_tokens, stop_ids, looks=None, pick=_argmax_pick, debug=None, check_every=16):
-        """Decode with ONE captured HIP graph per call: embed(token) -> 32 decode layers (GEMV projections, RoPE + KV append
-        and attention at the device-side cache length) -> final norm -> lm_head -> pick (argmax, or the draw + sample_rows of a _SamplePick)
-        -> next token, all on the device; the host replays the graph once per token (~450 kernel launches otherwise) and only looks at the
-        generated ids when `looks` says so — the token counts at which it does, increasing and ending at max_new_tokens; by default every
-        `check_every` tokens — to stop at one of `stop_ids`.  Tokens after the first stop are discarded, so the result equals the
-        token-by-token loop.  A generator: at every look it yields (generated ids so far, stopped, [hidden of each fed token])."""
-        cfg, dev, llm = self.config, self.device_, self.model.llm
-        d = cfg.hidden_size
-        logits = llm.next_token_logits(prefill_hidden[0, -1:])
-        tok = pick(logits, 0)                                                             # first generated token, int64 [1] on the device
-        # [position of the fed token, keys after appending it] and, for a pick that draws, the number of the token being generated: one
-        # advance per replay bumps them all
-        needs_step = getattr(pick, "needs_step", False)
-        counters = torch.tensor([S, S + 1] + ([1] if needs_step else []), dtype=torch.int32, device=dev)
-        step_dev = counters[2:3] if needs_step else None
-        toks = torch.empty(max_new_tokens, dtype=torch.int64, device=dev)
-        hid_all = torch.empty((max_new_tokens, d), dtype=torch.bfloat16, device=dev)
-        toks[0:1].copy_(tok)
-        h_static = torch.empty((1, 1, d), dtype=torch.bfloat16, device=dev)
-        # the gate's random draws (moe_gate_sampling) are keyed on the forward-pass number: the token-by-token loop gives the decode step
-        # of token i pass pass0 + i, so the graph reads it from a device counter it advances itself
-        pass0 = llm.gate_pass
-        pass_dev = torch.tensor([pass0 + 1], dtype=torch.int32, device=dev)
-        n_dbg = len(debug) if debug is not None else 0
-        static = {}
-
-        def note(row, i):                    # debug (tests): the logits, the draw and the token of generated token i, read back at once
-            u = getattr(pick, "last_u", None)
-            debug.append((row[0].float().cpu(), None if u is None else float(u[0]), int(toks[i])))
-
-        if debug is not None:
-            note(logits, 0)
-
-        def step():
-            emb = ops.splice_rows(llm.embed_tokens, None, tok, d)
-            h = llm.decode_step(emb.view(1, 1, d), cache, counters, pass_dev=pass_dev)
-            h_static.copy_(h)
-            static["logits"] = llm.next_token_logits(h[0, -1:])
-            tok.copy_(pick(static["logits"], step_dev))
-            ops.advance_ints(counters, 1)
-            ops.advance_ints(pass_dev, 1)
-
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(graph, stream=side):
-                step()
-        torch.cuda.current_stream().wait_stream(side)
-        if looks is None:
-            looks = list(range(1 + check_every, max_new_tokens, check_every)) + [max_new_tokens]
-        n, done = 1, False
-        try:
-            for upto in looks:
-                for i in range(n, upto):
-                    graph.replay()                                   # feeds token i-1, produces token i
-                    hid_all[i - 1:i].copy_(h_static.view(1, d))
-                    toks[i:i + 1].copy_(tok)
-                    if debug is not None:
-                        note(static["logits"], i)
-                # the only host synchronisation of the loop: the ids and the cache's error word (MP_POS_ERR_*) in one copy
-                got = torch.cat([toks[:upto], cache["err"].to(torch.int64)]).cpu().tolist()
-                err = got.pop()
-                if err:
-                    raise RuntimeError(f"_decode_graph: decode steps {n}..{upto - 1} (positions {S + n - 1}..{S + upto - 2}) ran past the RoPE table "
-                                       f"({llm.cos.shape[0]} rows) or the KV cache ({cache['k'][0].shape[1]} rows): error word {err}")
-                n = upto
-                hits = [i for i, t in enumerate(got) if t in stop_ids]
-                if hits:
-                    n = hits[0] + 1
-                    done = True
-                yield got[:n], done, [hid_all[i:i + 1].view(1, 1, d) for i in range(n - 1)]
-                if done:
-                    break
-        finally:                                 # (also when the consumer stops reading early)
-            llm.gate_pass = pass0 + n - 1        # the passes the loop would have made (replays past the first stop are discarded)
-            llm._draws_key = None                # (the captured draw buffer belongs to the graph)
-            if debug is not None:
-                del debug[n_dbg + n:]
-
-    def _graph_decode_ok(self):
-        """Whether _decode_graph computes what the token-by-token loop computes for this model: top-1, or top-2 on one rank without the
-        residual MoE and without injected gate draws (a host-side provider would be frozen into the graph)."""
-        cfg, llm = self.config, self.model.llm
-        if cfg.top_k_experts == 1:
-            return True
-        return cfg.top_k_experts == 2 and llm.ep is None and not cfg.use_residual and llm.rts_uniform_provider is None
-
-    def _decode(self, ids, images_clip, max_new_tokens, stop_ids, mask_images=None, image_token_types=None, image_token_lengths=None,
-                region_masks=None, valid_region_masks_bool=None, pick=_argmax_pick, looks=None, host_pick=False, debug=None):
-        """Prefill of the spliced prompt, then single-token decode steps against the KV cache, the next token chosen by `pick` (the greedy
-        argmax unless told otherwise), until one of `stop_ids` or max_new_tokens.  Through the captured graph when the model allows it
-        (decode_with_graph, _graph_decode_ok(), more than two tokens) and the pick runs on the device (not host_pick), else token by token.
-        A generator of (generated ids so far, stopped, [hidden states of the prompt, of each fed token]): the graph path yields at `looks`
-        (_decode_graph), the loop after every token."""
-        cfg, dev, m = self.config, self.device_, self.model
-        plan, feats = self._encode_and_plan(ids, None, None, images_clip, mask_images, image_token_types, image_token_lengths,
-                                            with_seg=False, region_masks=region_masks if region_masks else None,
-                                            valid_region_masks_bool=valid_region_masks_bool)
-        src = _h2d(plan.src_code.reshape(-1), dev)
-        S = plan.seq_len
-        embeds = ops.splice_rows(m.llm.embed_tokens, feats, src, cfg.hidden_size).view(1, S, cfg.hidden_size)
-        cache = m.llm.new_kv_cache(1, S + max_new_tokens)
-        hidden, _, _ = m.llm.forward(embeds, None, kv_cache=cache)
-        if self.decode_with_graph and max_new_tokens > 2 and self._graph_decode_ok() and not host_pick:
-            self.last_decode_path = "graph"
-            for generated, stopped, step_hiddens in self._decode_graph(hidden, cache, S, max_new_tokens, stop_ids, looks, pick, debug):
-                yield generated, stopped, [hidden] + step_hiddens
-            return
-        self.last_decode_path = "loop"
-        generated, hiddens = [], [hidden]
-        last = hidden[0, -1:]
-        for i in range(max_new_tokens):
-            logits = m.llm.next_token_logits(last)
-            tok = int(pick(logits, i)[0])
-            generated.append(tok)
-            if debug is not None:
-                u = getattr(pick, "last_u", None)
-                debug.append((logits[0].float().cpu(), None if u is None else float(u[0]), tok))
-            if tok in stop_ids or len(generated) == max_new_tokens:
-                err = int(cache["err"][0])
-                if err:
-                    raise RuntimeError(f"_greedy: a decode step ran past the RoPE table or the KV cache: error word {err}")
-                yield generated, tok in stop_ids, hiddens
-                return
-            yield generated, False, hiddens
-            emb = ops.splice_rows(m.llm.embed_tokens, None, torch.tensor([tok], dtype=torch.int64, device=dev), cfg.hidden_size)
-            h, _, _ = m.llm.forward(emb.view(1, 1, -1), None, kv_cache=cache)
-            hiddens.append(h)
-            last = h[0, -1:]
-
-    def _greedy(self, ids, images_clip, max_new_tokens, eos_token_id, mask_images=None, image_token_types=None, image_token_lengths=None,
-                region_masks=None, valid_region_masks_bool=None, pick=_argmax_pick):
-        """HF `generate(do_sample=False, use_cache=True)` on one sample (MedPLIB.py:592-606; prepare_inputs_for_generation,
-        medplib_moe_llama.py:451-485): prefill of the spliced prompt, then single-token decode steps against the KV cache (_decode).
-        Returns (output_ids [1, L + n] on the host, [hidden states of the prompt, of each fed token])."""
-        generated, hiddens = [], []
-        for generated, _, hiddens in self._decode(ids, images_clip, max_new_tokens, (eos_token_id,), mask_images, image_token_types,
-                                                  image_token_lengths, region_masks, valid_region_masks_bool, pick=pick):
-            pass
-        return np.concatenate([ids, np.asarray(generated, dtype=np.int64)[None]], 1), list(hiddens)
-
-    @torch.no_grad()
-    def generate(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, **kwargs):
-        """The VQA entry the drivers use (`model.generate(input_ids, images=images_clip, attention_mask=..., max_new_tokens=...,
-        do_sample=False)`, vqa_infer.py:430-442): greedy decoding, one sample per call like the reference's loop (batch rows are
-        decoded one after the other).  Returns output ids [B, L + n_max] (right-padded with eos), prompt included, as HF does."""
-        # HF generate kwargs the reference driver passes (vqa_infer.py:430-442): accepted when they mean greedy decoding, refused
-        # loudly otherwise — sampling and beam search are not built
-        if kwargs.get("do_sample") or (kwargs.get("temperature") or 0) > 0 and kwargs.get("do_sample") is not False:
-            raise NotImplementedError("generate(): sampling (do_sample / temperature > 0) is not built here: call generate_sample() "
-                                      "(temperature, top-k, top-p); the shipped eval scripts decode greedily")
-        if (kwargs.get("num_beams") or 1) != 1:
-            raise NotImplementedError("generate(): beam search (num_beams > 1) is not built here: call generate_beam(); the shipped eval "
-                                      "scripts use num_beams=1")
-        unknown = set(kwargs) - _GENERATE_KWARGS
-        if unknown:
-            raise TypeError(f"generate(): unsupported arguments {sorted(unknown)}")
-        return self._generate_rows("generate", input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs, lambda b: _argmax_pick)
-
-    def _generate_rows(self, who, input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs, pick_of_row, decode_row=None):
-        """generate() / generate_sample() / generate_beam(): batch rows decoded one after the other, row b's next token chosen by
-        pick_of_row(b) — or the whole row decoded by decode_row(row ids, images, region masks, their flags) -> ids [1, L + n]; output ids
-        [B, L + n_max], prompt included, right-padded with eos."""
-        self._require_shadowable(who)
-        self.sync_side_streams()
-        ids = _np_ids(input_ids).astype(np.int64)
-        was_training = self.training
-        self.train(False)
-        rows = []
-        with self.adapters_merged():                 # adapters attached: decode on their shadow merge, restored on the way out
-            for b in range(ids.shape[0]):
-                row = ids[b:b + 1]
-                if attention_mask is not None:
-                    row = row[:, _np_ids(attention_mask)[b].astype(bool)]               # drop this row's padding
-                img = images[b] if isinstance(images, (list, tuple)) else images[b:b + 1]
-                if isinstance(images, (list, tuple)):
-                    img = [img]
-                rm, rv = kwargs.get("region_masks") or (), kwargs.get("valid_region_masks_bool") or ()
-                if len(rm) > 0:            # the collator's flat list holds one entry per sample WITH regions: pick this row's
-                    before = sum(1 for v in rv[:b] if any(v))
-                    rm, rv = (rm[before:before + 1] if any(rv[b]) else ()), rv[b:b + 1]
-                if decode_row is not None:
-                    out = decode_row(row, img, rm, rv)
-                else:
-                    out, _ = self._greedy(row, img, max_new_tokens, eos_token_id, kwargs.get("mask_images"), kwargs.get("image_token_types"),
-                                          kwargs.get("image_token_lengths"), rm, rv, pick=pick_of_row(b))
-                rows.append(out[0])
-        self.train(was_training)
-        n = max(r.shape[0] for r in rows)
-        return torch.from_numpy(np.stack([np.concatenate([r, np.full(n - r.shape[0], eos_token_id, np.int64)]) for r in rows]))
-
-    @torch.no_grad()
-    def generate_sample(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, temperature=1.0, top_k=50,
-                        top_p=1.0, sample_seed=None, **kwargs):
-        """generate() with HF's do_sample=True (what vqa_infer.py:430-442 asks for with --temperature > 0): every next token is drawn from
-        softmax(logits / temperature) truncated by top-k, then top-p (HF 4.31's TemperatureLogitsWarper -> TopKLogitsWarper ->
-        TopPLogitsWarper; top_k = 50 is its GenerationConfig default, top_p=None means 1.0), by inverse CDF at the keyed generator's
-        uniforms (_SamplePick, ops.sample_rows_filtered): HF's distribution, not torch.multinomial's draws.  Row b draws under seed
-        sample_seed + b; sample_seed=None takes one from torch's global generator, as the serving worker does, so torch.manual_seed makes
-        a run repeatable.  Same return layout as generate(): prompt included, right-padded with eos.  temperature <= 0 raises ValueError
-        as HF does; beam search and repetition penalty are not built."""
-        if not float(temperature) > 0:
-            raise ValueError(f"generate_sample(): temperature={temperature} has to be a strictly positive float (greedy decoding: generate())")
-        if (kwargs.get("num_beams") or 1) != 1:
-            raise NotImplementedError("generate_sample(): beam search (num_beams > 1) is not built; the shipped eval scripts use num_beams=1")
-        unknown = set(kwargs) - {"do_sample", "num_beams", "use_cache", "mask_images", "image_token_types", "image_token_lengths", "region_masks",
-                                 "valid_region_masks_bool", "output_hidden_states", "return_dict_in_generate", "pad_token_id"}
-        if unknown:
-            raise TypeError(f"generate_sample(): unsupported arguments {sorted(unknown)}")
-        if kwargs.get("do_sample") is False:
-            raise ValueError("generate_sample(): do_sample=False asks for greedy decoding: call generate()")
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,))) if sample_seed is None else int(sample_seed)
-        top_k, top_p = int(top_k or 0), 1.0 if top_p is None else float(top_p)
-        return self._generate_rows("generate_sample", input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs,
-                                   lambda b: _SamplePick(temperature, seed + b, self.device_, top_k=top_k, top_p=top_p))
-
-    @torch.no_grad()
-    def generate_beam(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, num_beams=4, length_penalty=1.0,
-                      early_stopping=False, debug=None, **kwargs):
-        """generate() with HF 4.31's beam search (GenerationMixin.beam_search + BeamSearchScorer; what vqa_infer.py:430-442 asks for with
-        --num_beams > 1): generate(num_beams=, do_sample=False, num_return_sequences=1, length_penalty=, early_stopping=False | True), one
-        sample at a time.  The num_beams beams of a prompt are the rows of one decode step: they share the position counter and one pass over
-        the weights.  Between two steps the device ranks the candidates (ops.beam_topk) and re-orders the generated tail of the KV cache by
-        the chosen parents (ops.kv_permute_rows); the hypotheses live on the host (medplib_amd.beam.BeamScorer, replayed over the recorded
-        candidates at every look).  Decode path (last_decode_path): the captured graph under generate()'s conditions, else a token-by-token
-        loop that re-orders the whole cache with index_select.  Same return layout as generate(): prompt included, right-padded with eos; an
-        answer that ended on eos carries it when it fits, as HF's finalize writes it.  last_beam_scores: the winner's score per row.
-        Refused: do_sample=True (beam sampling), num_return_sequences != 1, early_stopping="never", num_beams > 8.
-        debug: a list that receives one dict per kept step — the fp32 logits [num_beams, V] on the host, the input beam scores, the candidates
-        and the selection (tests; costs a sync per token)."""
-        if kwargs.get("do_sample") or (kwargs.get("temperature") or 0) > 0 and kwargs.get("do_sample") is not False:
-            raise NotImplementedError("generate_beam(): beam sampling (do_sample / temperature > 0 with num_beams > 1) is not built")
-        if (kwargs.get("num_return_sequences") or 1) != 1:
-            raise NotImplementedError("generate_beam(): num_return_sequences != 1 is not built: the best beam is returned")
-        if early_stopping not in (False, True):
-            raise NotImplementedError(f"generate_beam(): early_stopping={early_stopping!r} is not built (False or True)")
-        nb = int(num_beams)
-        if not 1 <= nb <= 8:
-            raise NotImplementedError(f"generate_beam(): num_beams={num_beams} is not built: 1 to 8 beams share one decode step")
-        unknown = set(kwargs) - _GENERATE_KWARGS - {"num_return_sequences"}
-        if unknown:
-            raise TypeError(f"generate_beam(): unsupported arguments {sorted(unknown)}")
-        max_new_tokens = int(max_new_tokens)
-        assert max_new_tokens >= 1
-        self.last_beam_scores = []
-
-        def decode_row(row, img, rm, rv):
-            new, score = self._beam_row(row, img, max_new_tokens, int(eos_token_id), nb, float(length_penalty), bool(early_stopping),
-                                        kwargs.get("mask_images"), kwargs.get("image_token_types"), kwargs.get("image_token_lengths"), rm, rv, debug)
-            self.last_beam_scores.append(score)
-            return np.concatenate([row, np.asarray(new, dtype=np.int64)[None]], 1)
-
-        return self._generate_rows("generate_beam", input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs, None, decode_row)
-
-    def _beam_row(self, ids, images_clip, max_new_tokens, eos_token_id, nb, length_penalty, early_stopping, mask_images, image_token_types,
-                  image_token_lengths, region_masks, valid_region_masks_bool, debug, check_every=16):
-        """Beam search on one sample -> (generated ids of the winning hypothesis, its score).  Prefill at batch 1 — the launches of _decode —
-        into row 0 of a cache of nb rows, the prompt's K/V copied to the other rows; then one decode step per token at B = nb.  The step's
-        record (cand_score | cand_index | next_scores | next_parent | next_tokens, one buffer) is the state the next step reads and is copied
-        to a history row after every step; BeamScorer replays the history on the host."""
-        from ..beam import BeamScorer
-        cfg, dev, m = self.config, self.device_, self.model
-        llm, d = m.llm, cfg.hidden_size
-        plan, feats = self._encode_and_plan(ids, None, None, images_clip, mask_images, image_token_types, image_token_lengths,
-                                            with_seg=False, region_masks=region_masks if region_masks else None,
-                                            valid_region_masks_bool=valid_region_masks_bool)
-        src = _h2d(plan.src_code.reshape(-1), dev)
-        S = plan.seq_len
-        embeds = ops.splice_rows(llm.embed_tokens, feats, src, d).view(1, S, d)
-        cache = llm.new_kv_cache(nb, S + max_new_tokens)
-        row0 = {"len": 0, "k": [t[:1] for t in cache["k"]], "v": [t[:1] for t in cache["v"]], "err": cache["err"]}
-        hidden, _, _ = llm.forward(embeds, None, kv_cache=row0)
-        cache["len"] = S
-        if nb > 1:
-            for t in cache["k"] + cache["v"]:
-                t[1:, :S].copy_(t[:1, :S])
-        # the step record: one buffer, so that one copy files a step
-        rec = torch.zeros(32 * nb, dtype=torch.uint8, device=dev)
-        cs, ci = rec[:8 * nb].view(torch.float32), rec[8 * nb:16 * nb].view(torch.int32)
-        ns, par, tok = rec[16 * nb:20 * nb].view(torch.float32), rec[20 * nb:24 * nb].view(torch.int32), rec[24 * nb:].view(torch.int64)
-        hist = torch.empty((max_new_tokens, 32 * nb), dtype=torch.uint8, device=dev)
-        first_scores = [0.0] + [-1e9] * (nb - 1)                  # HF's beam_scores[:, 1:] = -1e9: the first step ranks one row
-        ns.copy_(torch.tensor(first_scores, dtype=torch.float32))
-        scorer = BeamScorer(nb, length_penalty, early_stopping, eos_token_id, length_base=ids.shape[1], max_new_tokens=max_new_tokens)
-        n_dbg = len(debug) if debug is not None else 0
-        scores_in = [torch.tensor(first_scores, dtype=torch.float32)]
-
-        def unpack(row):
-            """A history row on the host -> (cand_score, cand_index, next_scores, next_parent, next_tokens)."""
-            return (row[:8 * nb].view(np.float32), row[8 * nb:16 * nb].view(np.int32), row[16 * nb:20 * nb].view(np.float32),
-                    row[20 * nb:24 * nb].view(np.int32), row[24 * nb:].view(np.int64))
-
-        def note(logits):                    # debug (tests): this step's logits, input scores, candidates and selection, read back at once
-            c_s, c_i, n_s, n_p, n_t = unpack(rec.cpu().numpy())
-            debug.append({"logits": logits.float().cpu().expand(nb, -1), "scores_in": scores_in[0], "cand_score": c_s, "cand_index": c_i,
-                          "next_scores": n_s, "next_parent": n_p, "next_tokens": n_t})
-            scores_in[0] = torch.from_numpy(n_s.copy())
-
-        def feed(rows, err):
-            """The scorer over recorded steps, until done -> done."""
-            if err:
-                raise RuntimeError(f"_beam_row: a decode step ran past the RoPE table ({llm.cos.shape[0]} rows) or the KV cache "
-                                   f"({cache['k'][0].shape[1]} rows), or the beam selection ran out of candidates (NaN logits): error word {err}")
-            V = cfg.vocab_size
-            for row in rows:
-                c_s, c_i, _, _, _ = unpack(row)
-                if scorer.step([(float(s), int(i) // V, int(i) % V) for s, i in zip(c_s, c_i)]):
-                    return True
-            return False
-
-        def step_out(logits, shared=False):
-            ops.beam_topk(logits, ns, eos_token_id, cs, ci, ns, tok, par, cache["err"], nb=nb if shared else None)
-
-        logits = llm.next_token_logits(hidden[0, -1:])
-        assert logits.shape[1] == cfg.vocab_size
-        step_out(logits, shared=True)
-        hist[0].copy_(rec)
-        if debug is not None:
-            note(logits)
-        pass0 = llm.gate_pass
-        try:
-            if self.decode_with_graph and max_new_tokens > 2 and self._graph_decode_ok():
-                self.last_decode_path = "graph"
-                counters = torch.tensor([S, S + 1], dtype=torch.int32, device=dev)
-                pass_dev = torch.tensor([pass0 + 1], dtype=torch.int32, device=dev)
-                table, kept_alive = ops.kv_permute_table(cache)
-                static = {}
-
-                def step():
-                    ops.kv_permute_rows(table, cache["k"][0], par, S, counters[0:1], cache["err"])     # the tail follows the chosen parents
-                    emb = ops.splice_rows(llm.embed_tokens, None, tok, d)
-                    h = llm.decode_step(emb.view(nb, 1, d), cache, counters, pass_dev=pass_dev)
-                    static["logits"] = llm.next_token_logits(h.view(nb, d))
-                    step_out(static["logits"])
-                    ops.advance_ints(counters, 1)
-                    ops.advance_ints(pass_dev, 1)
-
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream())
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(side):
-                    with torch.cuda.graph(graph, stream=side):
-                        step()
-                torch.cuda.current_stream().wait_stream(side)
-                n = 1
-                for upto in list(range(1 + check_every, max_new_tokens, check_every)) + [max_new_tokens]:
-                    for i in range(n, upto):
-                        graph.replay()                               # feeds the tokens of step i-1, records step i
-                        hist[i].copy_(rec)
-                        if debug is not None:
-                            note(static["logits"])
-                    # the only host synchronisation of the loop: the steps' records and the cache's error word in one copy
-                    got = torch.cat([hist[scorer.steps:upto].reshape(-1), cache["err"].view(torch.uint8)]).cpu().numpy()
-                    n = upto
-                    if feed(got[:-4].reshape(-1, 32 * nb), int(got[-4:].view(np.int32)[0])):
-                        break
-            else:
-                self.last_decode_path = "loop"
-                for i in range(max_new_tokens):
-                    if feed(hist[i:i + 1].cpu().numpy(), int(cache["err"][0])) or i == max_new_tokens - 1:
-                        break
-                    if nb > 1:                                       # HF's _reorder_cache: the whole cache, by the chosen parents
-                        sel = par.to(torch.int64)
-                        cache["k"] = [t.index_select(0, sel) for t in cache["k"]]
-                        cache["v"] = [t.index_select(0, sel) for t in cache["v"]]
-                    emb = ops.splice_rows(llm.embed_tokens, None, tok.clone(), d)
-                    h, _, _ = llm.forward(emb.view(nb, 1, d), None, kv_cache=cache)
-                    logits = llm.next_token_logits(h.view(nb, d))
-                    step_out(logits)
-                    hist[i + 1].copy_(rec)
-                    if debug is not None:
-                        note(logits)
-        finally:
-            llm.gate_pass = pass0 + max(scorer.steps, 1) - 1        # the passes of the kept steps (replays past `done` are discarded)
-            llm._draws_key = None                                    # (a captured draw buffer belongs to its graph)
-            if debug is not None:
-                del debug[n_dbg + scorer.steps:]
-        return scorer.finalize()
-
-    @torch.no_grad()
-    def generate_stream(self, input_ids, images_clip, images=None, temperature=1.0, top_p=1.0, max_new_tokens=256, stop_token_id=None,
-                        eos_token_id=2, stream_interval=1, sample_seed=0, resize_list=None, original_size_list=None, region_masks=(),
-                        valid_region_masks_bool=(), attention_mask=None, uniforms=None, debug=None, stop_check=None, top_k=0, apply_top_p=False):
-        """The serving worker's token loop (model/serve/model_worker.py generate_stream) on one sample, as a generator: prefill, then one
-        decode step per token, yielding (new token ids so far, stopped, pred_mask) after tokens i with i % stream_interval == 0, after the
-        last one (i == max_new_tokens - 1) and at a stop (eos_token_id, stop_token_id, or stop_check(ids) -> True at a yield: the worker's
-        stop string).  Every yield's ids are a prefix of the next one's.
-
-        temperature < 1e-4: greedy, the tokens of generate().  Otherwise token i is drawn from softmax(logits / temperature) by inverse CDF
-        (ops.sample_rows) at the uniform the keyed generator gives for (sample_seed, i) (ops.sample_uniform): one seed, one answer; the
-        stream matches torch.multinomial in distribution, not draw by draw.  apply_top_p=False (the default): top_p is accepted and
-        IGNORED, as is top_k — the reference's worker reads top_p from the request and never uses it.  apply_top_p=True: the distribution
-        is truncated before the draw by top_k (0: none), then top_p, as HF's warpers do (ops.sample_rows_filtered), in the loop and in the
-        captured step alike.
-        Decode path (last_decode_path): the captured graph when decode_with_graph and _graph_decode_ok() hold, max_new_tokens > 2 and no
-        `uniforms` is injected; the draw and the pick are then part of the captured step, and the host looks at the ids (and the cache's error
-        word) only at the yields.  Otherwise the token-by-token loop.  uniforms(i) -> float replaces the generator (tests); it runs on the
-        host, so it forces the loop.
-        pred_mask is None except in the stopping yield (an answer that runs into max_new_tokens gets none, as in the reference), and
-        there only when `images` (the SAM input, with resize_list and original_size_list as in evaluate()) was given and a generated id
-        is seg_token_idx: evaluate()'s mask of the first <SEG>.
-        debug: a list that receives (fp32 logits row on the host, u or None, token) for every kept token (tests; costs a sync per token)."""
-        self._require_shadowable("generate_stream")
-        self.sync_side_streams()
-        ids = _np_ids(input_ids).astype(np.int64)
-        assert ids.shape[0] == 1, "generate_stream() decodes one sample, like the reference's worker"
-        if attention_mask is not None:
-            ids = ids[:, _np_ids(attention_mask)[0].astype(bool)]
-        max_new_tokens, every = int(max_new_tokens), max(1, int(stream_interval))
-        assert max_new_tokens >= 1
-        if temperature < 1e-4:
-            pick = _argmax_pick
-        elif apply_top_p:
-            pick = _SamplePick(temperature, sample_seed, self.device_, uniforms, top_k=top_k, top_p=1.0 if top_p is None else top_p)
-        else:
-            pick = _SamplePick(temperature, sample_seed, self.device_, uniforms)
-        stop_ids = {int(t) for t in (eos_token_id, stop_token_id) if t is not None}
-        due = lambda i: i % every == 0 or i == max_new_tokens - 1            # noqa: E731  the reference's condition on the token number
-        looks = [i + 1 for i in range(max_new_tokens) if due(i)]
-        was_training = self.training
-        shadow = contextlib.ExitStack()
-        shadow.enter_context(self.adapters_merged())         # adapters attached: their shadow merge lives as long as this generator
-        self.train(False)
-        steps = self._decode(ids, images_clip, max_new_tokens, stop_ids, region_masks=region_masks, valid_region_masks_bool=valid_region_masks_bool,
-                             pick=pick, looks=looks, host_pick=uniforms is not None, debug=debug)
-        try:
-            for generated, stopped, hiddens in steps:
-                i = len(generated) - 1
-                if not (stopped or due(i)):
-                    continue
-                new = list(generated)
-                if not stopped and stop_check is not None and stop_check(new):
-                    stopped = True
-                pred_mask = None
-                if stopped and images is not None and self.seg_token_idx in new:
-                    output_ids = np.concatenate([ids, np.asarray(new, dtype=np.int64)[None]], 1)
-                    pred_mask = self._seg_mask(output_ids, list(hiddens), images, resize_list, original_size_list)[0]
-                yield new, stopped, pred_mask
-                if stopped or i == max_new_tokens - 1:
-                    break
-        finally:
-            steps.close()
-            self.train(was_training)
-            shadow.close()
-
     def _seg_mask(self, output_ids, hiddens, images, resize_list, original_size_list, image_token_lengths=None):
         """The mask of one decoded sample (MedPLIB.py:608-680): the hidden state that predicts the first <SEG> of output_ids (position -2
         when there is none) -> text_hidden_fcs -> prompt + mask decoder over the SAM embedding of `images` -> [pred_mask [1, H, W]].
@@ -1258,35 +760,6 @@ class MedPLIBForCausalLM(nn.Module):
         shape = tuple(osz.shape[-2:]) if hasattr(osz, "shape") else tuple(osz)
         _, pred_masks = self._postprocess(low_res, resize_list[:1], [shape])
         return pred_masks
-
-    # ------------------------------------------------------------------ evaluate (MedPLIB.py:574-680)
-    @torch.no_grad()
-    def evaluate(self, images_clip, images, input_ids, resize_list, original_size_list, region_masks=(), valid_region_masks_bool=(),
-                 max_new_tokens=512, tokenizer=None, attention_mask=None, inference_demo=False, mask_images=None,
-                 image_token_types=None, image_token_lengths=None, eos_token_id=2):
-        """Greedy generation with a KV cache (prefill + single-token decode steps), then one mask per sample from the hidden
-        state that predicts the first <SEG> (or position -2 when no <SEG> was generated) — MedPLIB.py:574-680.
-        Returns (output_ids [1, L + n_generated] int64 on the host, [pred_mask [1,H,W]]).
-
-        Reference quirk kept: the concatenated per-step hidden states cover the spliced prompt and the first n-1 generated
-        tokens (the last generated token is never fed back), i.e. one position FEWER than build_seg_token_mask(output_ids)
-        yields; the mask's final position is always False (shifted mask), so it is truncated to the hidden length."""
-        cfg, dev, m = self.config, self.device_, self.model
-        self._require_shadowable("evaluate")
-        self.sync_side_streams()
-        ids = _np_ids(input_ids).astype(np.int64)
-        assert ids.shape[0] == 1, "evaluate() decodes one sample at a time, like the reference's validate_seg (vqa_infer.py:528)"
-        was_training = self.training
-        self.train(False)
-        with self.adapters_merged():                 # adapters attached: decode on their shadow merge, restored on the way out
-            output_ids, hiddens = self._greedy(ids, images_clip, max_new_tokens, eos_token_id, mask_images, image_token_types, image_token_lengths,
-                                               region_masks, valid_region_masks_bool)
-        if (output_ids[:, 1:] == self.seg_token_idx).sum() == 0 and inference_demo:
-            self.train(was_training)
-            return torch.from_numpy(output_ids), []
-        pred_masks = self._seg_mask(output_ids, hiddens, images, resize_list, original_size_list, image_token_lengths)
-        self.train(was_training)
-        return torch.from_numpy(output_ids), pred_masks
 
 
 class LISAForCausalLM(MedPLIBForCausalLM):
