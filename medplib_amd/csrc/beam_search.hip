@@ -1,7 +1,7 @@
 // Beam search between two decode steps, on the device (HF 4.31 GenerationMixin.beam_search; the reference's vqa_infer.py:430-442 passes
 // --num_beams to generate()): the candidate selection over the nb beams' next-token logits, and the re-order of the KV cache by the chosen
 // parents (HF's _reorder_cache).  gfx950, wave64.  Both launches are capturable: no host read, no allocation.
-#include "common.h"
+#include "row_pick.h"
 
 #include <algorithm>
 
@@ -14,110 +14,46 @@ constexpr int CAND_MAX = 2 * BEAM_MAX;
 // module global), shared by every stream: calls on different streams of one device must not overlap.
 __device__ unsigned long long g_row_cands[BEAM_MAX * CAND_MAX];
 
-// A candidate as ONE unsigned 64-bit key whose order is the ranking: the order-preserving integer image of the value in the high word (larger
-// value first), the complement of the flat index b * cols + c in the low word (lower index first among equal values).  -0 is folded onto +0, so
-// equal values have equal high words.  Valid keys are > 0 (the image of -inf is 0x007fffff); 0 stands for "none".
+// A candidate as ONE unsigned 64-bit key whose order is the ranking: the order-preserving integer image of the value (row_pick::float_key) in
+// the high word (larger value first), the complement of the flat index b * cols + c in the low word (lower index first among equal values).
+// -0 is folded onto +0, so equal values have equal high words.  Valid keys are > 0 (the image of -inf is 0x007fffff); 0 stands for "none".
 __device__ __forceinline__ unsigned long long cand_key(float v, unsigned flat) {
-  unsigned b = __float_as_uint(v);
-  if (b == 0x80000000u) b = 0u;
-  const unsigned k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((unsigned long long)k << 32) | (unsigned long long)(~flat);
+  if (__float_as_uint(v) == 0x80000000u) v = 0.f;
+  return ((unsigned long long)row_pick::float_key(v) << 32) | (unsigned long long)(~flat);
 }
-__device__ __forceinline__ float key_value(unsigned long long key) {
-  const unsigned k = (unsigned)(key >> 32);
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+__device__ __forceinline__ float key_value(unsigned long long key) { return row_pick::key_float((unsigned)(key >> 32)); }
 __device__ __forceinline__ unsigned key_flat(unsigned long long key) { return ~(unsigned)key; }
 
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int o) {
-  const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// block all-reduces of 1024 threads with ONE barrier each: the 16 wave results go to one of two LDS slots in turn (a thread can only be two
-// reductions ahead of the slowest after passing the barrier of the one between); the 16 wave results are combined in index order
-__device__ __forceinline__ float beam_block_fmax(float v, float (*red)[16], int& phase) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  float* s = red[phase];
-  phase ^= 1;
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = s[0];
-#pragma unroll
-  for (int i = 1; i < 16; ++i) t = fmaxf(t, s[i]);
-  return t;
-}
-__device__ __forceinline__ float beam_block_fsum(float v, float (*red)[16], int& phase) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  float* s = red[phase];
-  phase ^= 1;
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) t += s[i];
-  return t;
-}
-__device__ __forceinline__ unsigned long long beam_block_kmax(unsigned long long v, unsigned long long (*red)[16], int& phase) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long t = shfl_xor_u64(v, o);
-    v = t > v ? t : v;
-  }
-  unsigned long long* s = red[phase];
-  phase ^= 1;
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  unsigned long long t = s[0];
-#pragma unroll
-  for (int i = 1; i < 16; ++i) t = s[i] > t ? s[i] : t;
-  return t;
-}
-
-// Launch 1: one block of 1024 threads per beam, the row in the piece layout of the sampling kernels (piece p = tid + k * 1024 covers columns
-// 4p .. 4p + 3; up to 32768 columns the row stays in registers, wider rows are read again from L2 in every round).
+// Launch 1: one block per beam in the geometry of row_pick.h (up to 32768 columns the row stays in registers, wider rows are read again from
+// L2 in every round).
 //   m = the row maximum, Z = sum exp(l - m): NaN columns are left out of both (and are never candidates).  A row whose maximum is not finite
 //   (all -inf, all NaN, a +inf) has no candidates.
-//   v(c) = ((l_c - m) - log Z) + score: fp32; Z is summed in ONE fixed order (a thread's columns in order, the xor tree over the lanes, the 16
-//   wave sums in index order), so v has the same bits on every launch, for every alignment of the row.
+//   v(c) = ((l_c - m) - log Z) + score: fp32; Z is summed in ONE fixed order (a thread's columns in order, then row_pick::block_sum's), so v
+//   has the same bits on every launch, for every alignment of the row.
 //   2 * nb rounds of a block arg-max over the keys strictly below the previous pick: the row's 2 * nb best in rank order, ties by construction.
 template <int K, bool KEEP>
 __global__ __launch_bounds__(1024) void beam_row_topk_kernel(const float* __restrict__ x, int64_t ld, int nb, int cols,
                                                              const float* __restrict__ beam_scores) {
-  __shared__ float redf[2][16];
+  using namespace row_pick;
+  __shared__ unsigned redf[2][16];
   __shared__ unsigned long long redk[2][16];
   const int beam = blockIdx.x, tid = threadIdx.x;
   const float* r = x + (int64_t)beam * ld;
-  const bool wide = (reinterpret_cast<uintptr_t>(r) & 15) == 0;       // (block-uniform)
-  const float pad = __uint_as_float(0x7fc00000u);                     // columns at or past `cols`: NaN
+  const bool wide = starts_on_16_bytes(r);
+  auto piece = [&](int k) { return load_piece(r, wide, cols, __uint_as_float(0x7fc00000u), k); };      // columns at or past `cols`: NaN
   const float score = beam_scores[beam];
   int phase = 0, kphase = 0;
 
-  auto piece = [&](int k) {
-    const int i = 4 * (tid + k * 1024);
-    float4 p;
-    if (wide && i + 3 < cols) {
-      p = *reinterpret_cast<const float4*>(r + i);
-    } else {                                 // the piece that straddles `cols`, pieces past it, and rows off 16 bytes
-      p.x = i < cols ? r[i] : pad;
-      p.y = i + 1 < cols ? r[i + 1] : pad;
-      p.z = i + 2 < cols ? r[i + 2] : pad;
-      p.w = i + 3 < cols ? r[i + 3] : pad;
-    }
-    return p;
-  };
   float4 v[KEEP ? K : 1];
-  constexpr int UN = KEEP ? K : 4;
+  constexpr int UN = unroll_of(K, KEEP);
   float m = -INFINITY;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const float4 p = piece(k);
     if constexpr (KEEP) v[k] = p;
-    m = fmaxf(m, fmaxf(fmaxf(p.x, p.y), fmaxf(p.z, p.w)));      // (fmaxf drops NaN)
+    m = fmaxf(m, piece_max(p));
   }
-  m = beam_block_fmax(m, redf, phase);
+  m = block_fmax(m, redf, phase);
   unsigned long long* out = g_row_cands + beam * CAND_MAX;
   if (!(m > -INFINITY && m < INFINITY)) {                       // no candidates (block-uniform)
     if (tid < 2 * nb) out[tid] = 0ull;
@@ -130,7 +66,7 @@ __global__ __launch_bounds__(1024) void beam_row_topk_kernel(const float* __rest
     const float4 p = KEEP ? v[KEEP ? k : 0] : piece(k);
     z += ((w(p.x) + w(p.y)) + w(p.z)) + w(p.w);
   }
-  const float logz = logf(beam_block_fsum(z, redf, phase));
+  const float logz = logf(block_sum(z, redf, phase));
   auto value = [&](float l) { return ((l - m) - logz) + score; };       // NaN for a NaN column (and the padding)
   if constexpr (KEEP) {
 #pragma unroll
@@ -149,7 +85,7 @@ __global__ __launch_bounds__(1024) void beam_row_topk_kernel(const float* __rest
         p = piece(k);
         p.x = value(p.x); p.y = value(p.y); p.z = value(p.z); p.w = value(p.w);
       }
-      const unsigned i = flat0 + 4u * (unsigned)(tid + k * 1024);
+      const unsigned i = flat0 + (unsigned)piece_column(k);
       const float e[4] = {p.x, p.y, p.z, p.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -157,7 +93,7 @@ __global__ __launch_bounds__(1024) void beam_row_topk_kernel(const float* __rest
         if (key < prev && key > best) best = key;
       }
     }
-    best = beam_block_kmax(best, redk, kphase);
+    best = block_all_reduce(best, 0ull, [](unsigned long long a, unsigned long long b) { return b > a ? b : a; }, redk, kphase);
     if (tid == 0) out[round] = best;
     if (best == 0ull) {                       // the row ran out of candidates (block-uniform): the rest are none
       if (tid > round && tid < 2 * nb) out[tid] = 0ull;
@@ -266,10 +202,10 @@ extern "C" int mp_beam_topk_f32(const float* logits, int64_t ld, int nb, int col
   MP_REQUIRE(ld >= cols || ld == 0, MP_ERR_SHAPE, "mp_beam_topk_f32: ld=%lld < cols=%d (ld = 0: every beam reads the same row)", (long long)ld, cols);
   MP_REQUIRE(logits && beam_scores && cand_score && cand_index && next_scores && next_tokens && next_parent && err, MP_ERR_ARG,
              "mp_beam_topk_f32: null operand");
-  if (cols <= 32768)
-    hipLaunchKernelGGL((beam_row_topk_kernel<8, true>), dim3((unsigned)nb), dim3(1024), 0, stream, logits, ld, nb, cols, beam_scores);
-  else
-    hipLaunchKernelGGL((beam_row_topk_kernel<16, false>), dim3((unsigned)nb), dim3(1024), 0, stream, logits, ld, nb, cols, beam_scores);
+  row_pick::for_width(cols, [&](auto shape) {
+    using S = decltype(shape);
+    hipLaunchKernelGGL((beam_row_topk_kernel<S::K, S::KEEP>), dim3((unsigned)nb), dim3(1024), 0, stream, logits, ld, nb, cols, beam_scores);
+  });
   hipLaunchKernelGGL(beam_merge_kernel, dim3(1), dim3(64), 0, stream, nb, cols, eos_id, cand_score, cand_index, next_scores, next_tokens, next_parent,
                      err);
   return mp_check_launch("mp_beam_topk_f32");

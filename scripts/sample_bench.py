@@ -1,6 +1,7 @@
 """What temperature sampling costs on the device (generate_stream):
   1. microseconds per launch of mp_sample_rows_f32 against mp_argmax_rows_f32 on a [1, 32000] fp32 row — 200 launches captured into one HIP
-     graph and replayed, so the figure is the device's back-to-back time without the host's launch cost;
+     graph and replayed, so the figure is the device's back-to-back time without the host's launch cost; the same on a [1, 40000] row,
+     past the 32768 columns up to which the pick kernels hold the row in registers;
   2. milliseconds per token of the captured decode step with the sampling pick (draw + mp_sample_rows_f32) against the greedy pick (argmax),
      dense and MoE at bench.py's decode configuration (7B dims, batch 1, 64-token prompt): generate_stream's slope between two lengths
      (bench.py decode_rate's method: prefill and the graph capture cancel; the fastest of three calls per length after one untimed call),
@@ -84,9 +85,10 @@ def main():
     dev = torch.device("cuda:0")
     out = {"script": "python scripts/sample_bench.py --new %d" % args.new,
            "kernel_us_per_launch_1x32000": kernel_us(dev),
+           "kernel_us_per_launch_1x40000": kernel_us(dev, cols=40000),       # past 32768 columns: the kernels that read the row again
            "metric": "decode ms/token (generate_stream, captured graph, batch 1, KV cache, 7B dims, stream_interval 16)",
            "new_tokens": [args.new, 4 * args.new]}
-    print(json.dumps(out["kernel_us_per_launch_1x32000"]), flush=True)
+    print(json.dumps(out["kernel_us_per_launch_1x32000"]), json.dumps(out["kernel_us_per_launch_1x40000"]), flush=True)
     for name, cls, moe in (("dense", LISAForCausalLM, False), ("moe", MedPLIBForCausalLM, True)):
         model = cls(MedPLIBConfig.medplib_7b(moe_enable=moe), device=dev).eval()
         out[name] = step_ms(model, dev, args.new)

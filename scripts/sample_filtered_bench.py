@@ -1,7 +1,8 @@
 """What top-k / top-p truncation adds to temperature sampling on the device (scripts/sample_bench.py's protocol):
   1. microseconds per launch on a [1, 32000] fp32 row — 200 launches captured into one HIP graph and replayed — of mp_sample_rows_f32 and
      of mp_sample_filtered_rows_f32 at (k = 50, p = 0.9), (k = 0, p = 0.9) and (k = 50, p = 1), all in the same run, the graphs replayed
-     alternately; the ratios to the plain pick;
+     alternately; the ratios to the plain pick; the same on a [1, 40000] row, past the 32768 columns up to which the kernels hold the
+     row in registers;
   2. milliseconds per token of the captured decode step with the plain pick (draw + mp_sample_rows_f32) against the filtered pick
      (k = 50, p = 0.9), dense and MoE at bench.py's decode configuration (7B dims, batch 1, 64-token prompt): generate_stream's slope
      between two lengths (the fastest of three calls per length after one untimed call), the two picks measured alternately in the same
@@ -97,9 +98,10 @@ def main():
     out = {"script": "python scripts/sample_filtered_bench.py --new %d --models %s" % (args.new, args.models),
            "temperature": T,
            "kernel_us_per_launch_1x32000": kernel_us(dev),
+           "kernel_us_per_launch_1x40000": kernel_us(dev, cols=40000),       # past 32768 columns: the kernels that read the row again
            "metric": "decode ms/token (generate_stream, captured graph, batch 1, KV cache, 7B dims, stream_interval 16); filtered: top_k 50, top_p 0.9",
            "new_tokens": [args.new, 4 * args.new]}
-    print(json.dumps(out["kernel_us_per_launch_1x32000"]), flush=True)
+    print(json.dumps(out["kernel_us_per_launch_1x32000"]), json.dumps(out["kernel_us_per_launch_1x40000"]), flush=True)
     for name, cls, moe in (("dense", LISAForCausalLM, False), ("moe", MedPLIBForCausalLM, True)):
         if name not in args.models.split(","):
             continue
