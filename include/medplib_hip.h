@@ -114,6 +114,18 @@ int mp_gemm_bf16_nt_batched_rows(const void* A, int64_t lda, int64_t strideA, co
 int mp_gemv_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy, const float* bias,
                  const void* residual, int64_t ldr, const int* w_index, const float* row_scale, const int* row_keep, int M, int N, int K,
                  int act, int out_dtype, float alpha, hipStream_t stream);
+/* 8-bit decode weights (the reference worker's --load-8bit: model/serve/model_worker.py:72,100,642 -> builder.py:39, bitsandbytes' row-wise
+ * absmax format).  Quantiser, per row of W [rows, K] bf16 (ldw): scale[row] = absmax / 127 (fp32), codes[row, k] = rint(float(W[row, k]) *
+ * (127 / absmax)) half to even as int8 (ldc); every step one fp32 operation in that order; a zero row gets scale 0 and codes 0.  Called
+ * once per matrix (rows = E * N for an expert tensor), not on the hot path. */
+int mp_quantize_rows_w8_bf16(const void* W, int64_t ldw, int64_t rows, int K, void* codes, int64_t ldc, float* scale, hipStream_t stream);
+/* mp_gemv_bf16 on those codes (activations stay bf16): acc[m, n] = scale[n] * sum_k code[n, k] * x[m, k] in fp32, then mp_gemv_bf16's
+ * epilogues and rounding points (NONE, SWIGLU_PAIR, residual, fp32 output; the indexed expert form with W + w_index[m] * strideW and
+ * scale + w_index[m] * strideScale).  A row with row_keep[m] < 0 streams no weights: its output is the residual (0 without one), and the
+ * SWIGLU_PAIR form leaves its row unwritten.  No bias and no other activation (MP_ERR_ARG).  1 <= M <= 8, K % 16 == 0 (MP_ERR_SHAPE). */
+int mp_gemv_w8_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, const float* scale, int64_t strideScale, void* y,
+                    int64_t ldy, const float* bias, const void* residual, int64_t ldr, const int* w_index, const float* row_scale,
+                    const int* row_keep, int M, int N, int K, int act, int out_dtype, float alpha, hipStream_t stream);
 /* Top-2 MoE decode rows (tokens <= 8), the expert GEMVs over the 2 * tokens entries of mp_moe_route_top2's layout (entry c * tokens + t =
  * choice c of token t; expert[e], slot[e] < 0 = dropped, weight[e]).  gate|up: act[e, :N/2] = SwiGLU-paired x[t] . W[expert[e]] (W [E, N, K]
  * interleaved gate|up rows; dropped entries are skipped and their rows left unwritten).  down: y[t] = residual[t] + sum over the kept choices

@@ -4,7 +4,7 @@
 // flight per lane — against the x chunk it holds in registers, reduces across the wave, and applies the same fused epilogues as the
 // GEMM (bias, activation, residual, SwiGLU pairing over the interleaved gate|up rows).  MoE decode: `w_index[m]` (device) selects
 // the expert's weight matrix per row and `row_scale[m]` / `row_keep[m]` carry the top-1 gate probability and the capacity drop.
-#include "gemm_common.h"
+#include "gemv_epilogue.h"
 
 namespace {
 
@@ -50,16 +50,8 @@ template <int M, bool SWIGLU>
 __global__ __launch_bounds__(256) void gemv_shared_kernel(GemvArgs g) {
   const int lane = threadIdx.x & 63;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
-  // columns of this wave: plain = 4 consecutive; SWIGLU = gate rows {g0, g0+1} and their up rows {g0+32, g0+33}
   int rows[4];
-  if (SWIGLU) {
-    const int pair = wid * 2;                               // output column pair index
-    const int blk = pair >> 5, j = pair & 31;
-    rows[0] = blk * 64 + j; rows[1] = rows[0] + 1; rows[2] = rows[0] + 32; rows[3] = rows[0] + 33;
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rows[r] = wid * 4 + r;
-  }
+  gv_wave_rows<SWIGLU>(wid, rows);                          // plain: 4 consecutive columns; SWIGLU: two gate rows and their up rows
   if (rows[0] >= g.N) return;
   const bf16_t* wp[4];
 #pragma unroll
@@ -113,28 +105,11 @@ __global__ __launch_bounds__(256) void gemv_shared_kernel(GemvArgs g) {
 #pragma unroll
   for (int m = 0; m < M; ++m) {
     if (SWIGLU) {
-      bf16_t* yo = reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy;
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const float gf = (float)(bf16_t)(acc[m][p] * g.alpha), uf = (float)(bf16_t)(acc[m][2 + p] * g.alpha);
-        const int col = (rows[p] >> 6) * 32 + (rows[p] & 31);
-        if (rows[p] < g.N) yo[col] = (bf16_t)(gf * mp_sigmoid_fast(gf) * uf);
-      }
+      gv_swiglu_store(acc[m], rows, g.N, g.alpha, reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy);
     } else {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = rows[r];
-        if (n >= g.N) continue;
-        float v = apply_act(acc[m][r] * g.alpha + (g.bias ? g.bias[n] : 0.f), g.act);
-        if (g.out_f32) {
-          if (g.residual) v += (float)g.residual[(int64_t)m * g.ldr + n];
-          reinterpret_cast<float*>(g.y)[(int64_t)m * g.ldy + n] = v;
-        } else {
-          v = (float)(bf16_t)v;                              // same rounding points as the 256x256 GEMM epilogue
-          if (g.residual) v += (float)g.residual[(int64_t)m * g.ldr + n];
-          reinterpret_cast<bf16_t*>(g.y)[(int64_t)m * g.ldy + n] = (bf16_t)v;
-        }
-      }
+      for (int r = 0; r < 4; ++r)
+        if (rows[r] < g.N) gv_store_shared(g, m, rows[r], acc[m][r]);
     }
   }
 }
@@ -168,53 +143,29 @@ __device__ __forceinline__ void gv_indexed_row_dot(const bf16_t* __restrict__ xr
   for (int r = 0; r < 4; ++r) acc[r] = wave_sum(acc[r]);
 }
 
-// The indexed form's SwiGLU epilogue (lane 0): gate rows {g0, g0+1} and their up rows {g0+32, g0+33} -> two output columns.
-__device__ __forceinline__ void gv_swiglu_store(const float (&acc)[4], const int (&rows)[4], int N, bf16_t* __restrict__ yo) {
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const float gf = (float)(bf16_t)acc[p], uf = (float)(bf16_t)acc[2 + p];
-    const int col = (rows[p] >> 6) * 32 + (rows[p] & 31);
-    if (rows[p] < N) yo[col] = (bf16_t)(gf * mp_sigmoid_fast(gf) * uf);
-  }
-}
-
 // INDEXED: every row picks its own weight matrix (MoE experts); rows are processed one after the other
 template <bool SWIGLU>
 __global__ __launch_bounds__(256) void gemv_indexed_kernel(GemvArgs g) {
   const int lane = threadIdx.x & 63;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
   int rows[4];
-  if (SWIGLU) {
-    const int pair = wid * 2;
-    const int blk = pair >> 5, j = pair & 31;
-    rows[0] = blk * 64 + j; rows[1] = rows[0] + 1; rows[2] = rows[0] + 32; rows[3] = rows[0] + 33;
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rows[r] = wid * 4 + r;
-  }
+  gv_wave_rows<SWIGLU>(wid, rows);
   if (rows[0] >= g.N) return;
   for (int m = 0; m < g.M; ++m) {
     const bf16_t* Wm = g.W + (int64_t)g.w_index[m] * g.strideW;
-    float scale = g.row_scale ? g.row_scale[m] : 1.f;
-    if (g.row_keep && g.row_keep[m] < 0) scale = 0.f;
+    const float scale = gv_row_scale(g, m);
     const bf16_t* wp[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(rows[r], g.N - 1) * g.ldw;
     float acc[4];
     gv_indexed_row_dot(g.x + (int64_t)m * g.ldx, wp, g.K, lane, acc);
     if (lane != 0) continue;
-    bf16_t* yo = reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy;
     if (SWIGLU) {
-      gv_swiglu_store(acc, rows, g.N, yo);
+      gv_swiglu_store(acc, rows, g.N, 1.f, reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy);
     } else {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = rows[r];
-        if (n >= g.N) continue;
-        float v = scale * (float)(bf16_t)acc[r];            // combine: gate weight on the bf16-rounded expert output, then the residual
-        if (g.residual) v += (float)g.residual[(int64_t)m * g.ldr + n];
-        yo[n] = (bf16_t)v;
-      }
+      for (int r = 0; r < 4; ++r)
+        if (rows[r] < g.N) gv_store_indexed(g, m, rows[r], acc[r], scale);
     }
   }
 }
@@ -416,14 +367,7 @@ __global__ __launch_bounds__(256) void gemv_rmsnorm_kernel(GemvArgs g, const flo
   const int lane = threadIdx.x & 63;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
   int rows[4];
-  if (SWIGLU) {                                             // as gemv_shared_kernel: gate rows {g0, g0+1} and their up rows {g0+32, g0+33}
-    const int pair = wid * 2;
-    const int blk = pair >> 5, j = pair & 31;
-    rows[0] = blk * 64 + j; rows[1] = rows[0] + 1; rows[2] = rows[0] + 32; rows[3] = rows[0] + 33;
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rows[r] = wid * 4 + r;
-  }
+  gv_wave_rows<SWIGLU>(wid, rows);                          // as gemv_shared_kernel
   const bf16_t* wp[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) wp[r] = g.W + (int64_t)min(rows[r], g.N - 1) * g.ldw;
@@ -433,13 +377,7 @@ __global__ __launch_bounds__(256) void gemv_rmsnorm_kernel(GemvArgs g, const flo
 #pragma unroll
   for (int m = 0; m < M; ++m) {
     if (SWIGLU) {                                           // the shared kernel's SwiGLU epilogue, rounding points included
-      bf16_t* yo = reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy;
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const float gf = (float)(bf16_t)(acc[m][p] * g.alpha), uf = (float)(bf16_t)(acc[m][2 + p] * g.alpha);
-        const int col = (rows[p] >> 6) * 32 + (rows[p] & 31);
-        if (rows[p] < g.N) yo[col] = (bf16_t)(gf * mp_sigmoid_fast(gf) * uf);
-      }
+      gv_swiglu_store(acc[m], rows, g.N, g.alpha, reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy);
     } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -581,23 +519,8 @@ __global__ __launch_bounds__(1024) void gemv_ksplit_kernel(GemvArgs g) {
     const int n = row0 + lane;                               // lane r of the kp = 0 wave finishes row r of its group
     if (n >= g.N) continue;
     const float a = ((red[0][rg][lane] + red[1][rg][lane]) + red[2][rg][lane]) + red[3][rg][lane];
-    if (g.w_index) {                                        // gemv_indexed_kernel's epilogue: combine weight on the bf16-rounded expert output, then the residual
-      float scale = g.row_scale ? g.row_scale[m] : 1.f;
-      if (g.row_keep && g.row_keep[m] < 0) scale = 0.f;
-      float v = scale * (float)(bf16_t)a;
-      if (g.residual) v += (float)g.residual[(int64_t)m * g.ldr + n];
-      reinterpret_cast<bf16_t*>(g.y)[(int64_t)m * g.ldy + n] = (bf16_t)v;
-    } else {                                                // gemv_shared_kernel's
-      float v = apply_act(a * g.alpha + (g.bias ? g.bias[n] : 0.f), g.act);
-      if (g.out_f32) {
-        if (g.residual) v += (float)g.residual[(int64_t)m * g.ldr + n];
-        reinterpret_cast<float*>(g.y)[(int64_t)m * g.ldy + n] = v;
-      } else {
-        v = (float)(bf16_t)v;
-        if (g.residual) v += (float)g.residual[(int64_t)m * g.ldr + n];
-        reinterpret_cast<bf16_t*>(g.y)[(int64_t)m * g.ldy + n] = (bf16_t)v;
-      }
-    }
+    if (g.w_index) gv_store_indexed(g, m, n, a, gv_row_scale(g, m));      // gemv_indexed_kernel's epilogue
+    else gv_store_shared(g, m, n, a);                                      // gemv_shared_kernel's
   }
 }
 
@@ -621,7 +544,7 @@ __global__ __launch_bounds__(256) void gemv_top2_gate_up_kernel(GemvArgs g, int 
     for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(rows[r], g.N - 1) * g.ldw;
     float acc[4];
     gv_indexed_row_dot(g.x + (int64_t)(e % T) * g.ldx, wp, g.K, lane, acc);
-    if (lane == 0) gv_swiglu_store(acc, rows, g.N, reinterpret_cast<bf16_t*>(g.y) + (int64_t)e * g.ldy);
+    if (lane == 0) gv_swiglu_store(acc, rows, g.N, 1.f, reinterpret_cast<bf16_t*>(g.y) + (int64_t)e * g.ldy);
   }
 }
 

@@ -1,0 +1,58 @@
+// The epilogues of the decode-step GEMVs, shared by the bf16 kernels (gemv_bf16.hip) and the 8-bit-weight kernels (gemv_w8.hip): what happens
+// to a finished fp32 dot product `a` of output column n of row m.  `Args` is the kernel's argument block (GemvArgs / GemvW8Args: the same field
+// names).  The rounding points are those of the 256x256 GEMM epilogue, so a decode row and a prefill row round at the same places.
+#pragma once
+#include "gemm_common.h"
+
+// wave `wid`'s four W rows: plain = four consecutive; SWIGLU = gate rows {g0, g0+1} and their up rows {g0+32, g0+33} of the interleaved gate|up matrix
+template <bool SWIGLU>
+__device__ __forceinline__ void gv_wave_rows(int wid, int (&rows)[4]) {
+  if (SWIGLU) {
+    const int pair = wid * 2;                               // output column pair index
+    const int blk = pair >> 5, j = pair & 31;
+    rows[0] = blk * 64 + j; rows[1] = rows[0] + 1; rows[2] = rows[0] + 32; rows[3] = rows[0] + 33;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rows[r] = wid * 4 + r;
+  }
+}
+
+// shared-weight form: act(a * alpha + bias) -> [bf16 rounding] -> + residual
+template <class Args>
+__device__ __forceinline__ void gv_store_shared(const Args& g, int m, int n, float a) {
+  float v = apply_act(a * g.alpha + (g.bias ? g.bias[n] : 0.f), g.act);
+  if (g.out_f32) {
+    if (g.residual) v += (float)g.residual[(int64_t)m * g.ldr + n];
+    reinterpret_cast<float*>(g.y)[(int64_t)m * g.ldy + n] = v;
+  } else {
+    v = (float)(bf16_t)v;                                    // same rounding points as the 256x256 GEMM epilogue
+    if (g.residual) v += (float)g.residual[(int64_t)m * g.ldr + n];
+    reinterpret_cast<bf16_t*>(g.y)[(int64_t)m * g.ldy + n] = (bf16_t)v;
+  }
+}
+
+// indexed (expert) form: combine weight on the bf16-rounded expert output, then the residual
+template <class Args>
+__device__ __forceinline__ void gv_store_indexed(const Args& g, int m, int n, float a, float scale) {
+  float v = scale * (float)(bf16_t)a;
+  if (g.residual) v += (float)g.residual[(int64_t)m * g.ldr + n];
+  reinterpret_cast<bf16_t*>(g.y)[(int64_t)m * g.ldy + n] = (bf16_t)v;
+}
+
+// the combine weight of row m in the indexed form: row_scale[m] (1 without), 0 for a capacity-dropped row
+template <class Args>
+__device__ __forceinline__ float gv_row_scale(const Args& g, int m) {
+  float scale = g.row_scale ? g.row_scale[m] : 1.f;
+  if (g.row_keep && g.row_keep[m] < 0) scale = 0.f;
+  return scale;
+}
+
+// SwiGLU pairing (lane 0): gate rows {g0, g0+1} = acc[0..1] and their up rows {g0+32, g0+33} = acc[2..3] -> two output columns of yo
+__device__ __forceinline__ void gv_swiglu_store(const float (&acc)[4], const int (&rows)[4], int N, float alpha, bf16_t* __restrict__ yo) {
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const float gf = (float)(bf16_t)(acc[p] * alpha), uf = (float)(bf16_t)(acc[2 + p] * alpha);
+    const int col = (rows[p] >> 6) * 32 + (rows[p] & 31);
+    if (rows[p] < N) yo[col] = (bf16_t)(gf * mp_sigmoid_fast(gf) * uf);
+  }
+}

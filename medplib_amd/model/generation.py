@@ -340,9 +340,11 @@ class GenerationMixin:
         """The prologue and epilogue of a decode entry point: adapters under expert parallelism are refused before any state changes, the
         calling stream is ordered behind the side streams, the model is in eval mode and, with adapters attached, decodes on their shadow
         merge (adapters_merged()); leaving the block — also on an exception or when a generator is closed early — puts the plain weights
-        and the mode back.  Yields the ExitStack that holds the merge: close() it to have the plain weights back before the block ends."""
+        and the mode back.  In 8-bit mode (enable_decode_8bit) the copies are re-quantised here, before anything is captured, when the parameters were
+        written since they were made.  Yields the ExitStack that holds the merge: close() it to have the plain weights back before the block ends."""
         self._require_shadowable(who)
         self.sync_side_streams()
+        self._refresh_decode_8bit(who)
         was_training = self.training
         self.train(False)
         try:
@@ -351,6 +353,42 @@ class GenerationMixin:
                 yield merged
         finally:
             self.train(was_training)
+
+    # ------------------------------------------------------------------ 8-bit decode weights (the reference worker's --load-8bit)
+    @property
+    def decode_8bit(self):
+        """Whether the decode steps stream the 8-bit copies of the decoder projections."""
+        return self.model.llm.w8 is not None
+
+    def enable_decode_8bit(self, on=True):
+        """The reference worker's --load-8bit (model/serve/model_worker.py:72,100,642 -> builder.py:39, bitsandbytes) as a SPEED mode of the
+        decode steps, not a memory mode: int8 copies of the decoder's qkv, o, gate|up and down projections (row-wise absmax, bitsandbytes'
+        weight format; LlamaStack.quantize_decode_weights) are added beside the bf16 weights, and every single-token decode step of evaluate /
+        generate / generate_sample / generate_beam / generate_stream — captured or looped — streams them: half the bytes per token.  Prefill,
+        training and export keep the bf16 weights and their bits; lm_head, the embeddings, the norms and the MoE gate stay as they are; the
+        activations stay bf16 (W8A16: no int8 activations, no outlier split).  NotImplementedError, with the mode left as it was, for top-2
+        routing, the residual MoE, expert parallelism, attached adapters (merge_and_unload() first) and dimensions that are no multiple of 16.
+        enable_decode_8bit(False) drops the copies: today's path, bit for bit."""
+        llm = self.model.llm
+        if not on:
+            llm.drop_decode_weights_w8()
+            return self
+        self._refuse_in_shadow("enable_decode_8bit")
+        self.sync_side_streams()
+        llm.quantize_decode_weights()
+        return self
+
+    def _refresh_decode_8bit(self, who):
+        """The decode prologue's part in 8-bit mode: what enable_decode_8bit refuses may have been attached since (adapters, expert parallelism),
+        and an optimizer step or a checkpoint load (ops.PARAM_EPOCH) leaves the copies stale."""
+        llm = self.model.llm
+        if llm.w8 is None:
+            return
+        why = llm.decode_w8_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"{who}() in 8-bit decode mode: {why} (or enable_decode_8bit(False))")
+        if llm.w8_epoch != ops.PARAM_EPOCH:
+            llm.quantize_decode_weights()
 
     def _graph_decode_ok(self):
         """Whether the captured step computes what the token-by-token loop computes for this model: top-1, or top-2 on one rank without the

@@ -76,6 +76,8 @@ class LlamaStack:
         self._draws_all = None             # fp32 [L * T * E] gate draws of one pass, all layers: _gate_draws writes and slices
         self.fuse_moe_gather_scatter = True   # top-1, one rank: dispatch / combine folded into the expert GEMMs
         self.fuse_decode_routing = True       # decode rows: post-attention norm + gate + routing in one launch
+        self.w8 = None                     # 8-bit decode mode: per layer {"qkv" | "o" | "gu" | "down": (codes, scale)}, or None (off): quantize_decode_weights / drop_decode_weights_w8
+        self.w8_epoch = None               # ops.PARAM_EPOCH the copies were quantised at
         # RoPE in the qkv GEMM's epilogue (mp_gemm_qkv_rope_bf16) wants the q / k head rows interleaved in blocks of 32; the plain
         # fused qkv weight stays (decode GEMVs, the LoRA path's dgrad transposes, export), the interleaved copy (+3.2 GB of 288 at
         # 7B) serves every multi-row forward.  Rebuilt whenever the qkv weights change (refresh_fused_qkv).
@@ -101,6 +103,46 @@ class LlamaStack:
             if on and i in self.moe_layers:
                 lw["qkv_rope_f"] = (lw["qkv_rope"].float() * lw["ln1"][None, :]).to(torch.bfloat16)
                 lw["gu_f"] = (lw["gu"].float() * lw["ln2"][None, None, :]).to(torch.bfloat16)
+
+    W8_KEYS = ("qkv", "o", "gu", "down")
+
+    def decode_w8_unsupported(self):
+        """Why this stack cannot decode from 8-bit copies (a sentence), or None."""
+        cfg = self.cfg
+        if any(i in self.moe_layers for i in range(len(self.layers))) and cfg.top_k_experts != 1:
+            return "top-2 expert routing has no 8-bit expert GEMVs (top_k_experts == 1 only)"
+        if cfg.use_residual:
+            return "the residual MoE (use_residual) decodes through the GEMM path, which reads the bf16 weights"
+        if self.ep is not None:
+            return "expert parallelism keeps the experts sharded; the 8-bit expert GEMVs run on one rank"
+        if self.lora is not None:
+            return "attached adapters rewrite the bf16 weights under the 8-bit copies (adapters_merged()): call merge_and_unload() first"
+        if cfg.hidden_size % 16 or cfg.intermediate_size % 16:
+            return f"hidden_size={cfg.hidden_size} and intermediate_size={cfg.intermediate_size} must be multiples of 16 (16 codes per 16-byte load)"
+        return None
+
+    def quantize_decode_weights(self):
+        """8-bit decode mode on: row-wise absmax int8 copies (ops.quantize_rows_w8, bitsandbytes' weight format) of every layer's qkv, o, gate|up
+        and down projections, dense [N, K] and expert [E, N, K] alike (+ half the decoder's bf16 bytes; the bf16 weights stay and serve prefill,
+        training, export and the adapter merge).  While self.w8 is set, every decode row (decode_step, forward with a KV cache at pos0 > 0)
+        streams the copies.  lm_head, embed_tokens, the norms and the gate wg are not quantised.  Stamped with ops.PARAM_EPOCH: whoever decodes
+        re-quantises when the parameters were written since.  NotImplementedError (and nothing changed) where the mode is not built."""
+        why = self.decode_w8_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"8-bit decode weights: {why}")
+        self.w8 = [{k: ops.quantize_rows_w8(lw[k]) for k in self.W8_KEYS} for lw in self.layers]
+        self.w8_epoch = ops.PARAM_EPOCH
+
+    def drop_decode_weights_w8(self):
+        """8-bit decode mode off: the copies are dropped and every decode row reads the bf16 weights again."""
+        self.w8 = self.w8_epoch = None
+
+    def _row_proj(self, lw, key, a, q8, **kw):
+        """THE selector of a decode-row projection (at most 8 rows): the 8-bit GEMV on the layer's copies q8 (self.w8[i], handed down only
+        for a decode row) or the bf16 GEMV on lw[key]."""
+        if q8 is not None:
+            return ops.gemv_w8(a, *q8[key], **kw)
+        return ops.gemv(a, lw[key], **kw)
 
     def enable_expert_parallel(self, ep):
         """Shard the experts over an expert-parallel group (DeepSpeed `ep_size`, medplib_moe_llama.py:604-614): every rank keeps the
@@ -209,11 +251,14 @@ class LlamaStack:
         """Whether T rows of a MoE layer take the per-row expert GEMVs (the decode rows): one rank, at most 8 rows, no residual MoE."""
         return self.ep is None and T <= 8 and not self.cfg.use_residual
 
-    def _expert_gemvs_top1(self, lw, h, x, expert, slot, weight):
+    def _expert_gemvs_top1(self, lw, h, x, expert, slot, weight, q8=None):
         """Decode rows, top-1: each row streams its own expert's matrices (GEMV with a device-side expert index); the combine weight, the
         capacity drop and the residual ride in the down projection's epilogue.  Behind _mlp's routing and behind decode_step's fused one."""
-        act = ops.gemv(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR, w_index=expert)
-        return ops.gemv(act, lw["down"], residual=x, w_index=expert, row_scale=weight, row_keep=slot)
+        if q8 is not None:         # (the 8-bit gate|up also skips a dropped row's weights; its act row stays unwritten and the down projection never reads it)
+            act = self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR, w_index=expert, row_keep=slot)
+        else:
+            act = self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR, w_index=expert)
+        return self._row_proj(lw, "down", act, q8, residual=x, w_index=expert, row_scale=weight, row_keep=slot)
 
     def _expert_gemvs_top2(self, lw, h, x, expert, slot, weight):
         """Decode rows, top-2: the 2T (token, choice) entries stream their experts' matrices; the down projection adds both weighted expert
@@ -221,14 +266,14 @@ class LlamaStack:
         act = ops.gemv_top2_gate_up(h, lw["gu"], expert, slot)
         return ops.gemv_top2_down(act, lw["down"], expert, slot, weight, x)
 
-    def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None, pass_dev=None):
+    def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None, pass_dev=None, q8=None):
         """x + MLP(h): h = post-attention RMSNorm output [T,d], x = residual stream [T,d]; gate = (logits, gates) when the caller's fused
         norm kernel already produced them (ops.rmsnorm_gate); needed = (rows, mask) when only those output rows are read (the last layer);
-        rstd: the folded post-attention norm (h is None then).  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
+        rstd: the folded post-attention norm (h is None then); q8: the layer's 8-bit copies when the rows are decode rows.  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
         cfg, T = self.cfg, x.shape[0]
         if i not in self.moe_layers:
             if T <= 8:
-                return ops.gemv(ops.gemv(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR), lw["down"], residual=x), None, None
+                return self._row_proj(lw, "down", self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR), q8, residual=x), None, None
             act = ops.gemm(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR)       # silu(gate)*up fused into the GEMM epilogue
             return ops.gemm(act, lw["down"], residual=x), None, None
         E, k, cap = cfg.num_experts, cfg.top_k_experts, self.capacity(T)
@@ -237,7 +282,7 @@ class LlamaStack:
             # (no gate draws: random token selection only acts when an expert is over capacity; below cap >= T the draws are generated as usual)
             draws = None if cap >= T else self._gate_draws(i, T, E, False, pass_dev)
             expert, slot, weight, kept, counts, l_aux = ops.moe_route_top1(gates, cap, draws)
-            return self._expert_gemvs_top1(lw, h, x, expert, slot, weight), l_aux, (expert, slot, counts)
+            return self._expert_gemvs_top1(lw, h, x, expert, slot, weight, q8), l_aux, (expert, slot, counts)
         if k == 2 and self._expert_gemv_rows(T):
             expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2(gates, logits, cap, self._gate_draws(i, T, E, True, pass_dev))
             return self._expert_gemvs_top2(lw, h, x, expert, slot, weight), l_aux, (expert, slot, counts)
@@ -348,11 +393,12 @@ class LlamaStack:
                 "v": [torch.empty(shape, dtype=torch.bfloat16, device=self.device) for _ in self.layers],
                 "err": torch.zeros(1, dtype=torch.int32, device=self.device)}
 
-    def _lin(self, a, w, **kw):
-        """A projection of a [T, K]: a handful of rows (the single-token decode steps) are a weight stream -> GEMV kernel (HBM-bound), else GEMM."""
-        return ops.gemv(a, w, **kw) if a.shape[0] <= 8 else ops.gemm(a, w, **kw)
+    def _lin(self, lw, key, a, q8=None, **kw):
+        """The projection lw[key] of a [T, K]: a handful of rows (the single-token decode steps) are a weight stream -> GEMV kernel (HBM-bound,
+        _row_proj), else GEMM."""
+        return self._row_proj(lw, key, a, q8, **kw) if a.shape[0] <= 8 else ops.gemm(a, lw[key], **kw)
 
-    def _qkv(self, lw, x, S, pos0, folded):
+    def _qkv(self, lw, x, S, pos0, folded, q8=None):
         """input_layernorm + fused qkv projection + RoPE of the rows x [B*S, d] at positions pos0 .. pos0 + S - 1 -> qkv [B*S, 3d]."""
         cfg = self.cfg
         H, D, (T, d) = cfg.num_attention_heads, cfg.head_dim, x.shape
@@ -362,7 +408,7 @@ class LlamaStack:
         h = ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps)
         if self.fuse_rope and T > 8:       # RoPE in the epilogue (row stride of the qkv buffer kept off multiples of 8 KiB: ops.padded_rows)
             return ops.gemm_qkv_rope(h, lw["qkv_rope"], self.cos, self.sin, S, H, D, pos_offset=pos0, out=ops.padded_rows(T, 3 * d, x.device))
-        qkv = self._lin(h, lw["qkv"])
+        qkv = self._lin(lw, "qkv", h, q8)
         ops.rope_qk_(qkv, self.cos, self.sin, S, H, D, pos_offset=pos0)
         return qkv
 
@@ -400,9 +446,12 @@ class LlamaStack:
             and d in ops.RMSNORM_GATE_DIMS and ops.gemm_fold_ok(B * S, 3 * d, d) and ops.gemm_fold_ok(self.capacity(B * S), 2 * cfg.intermediate_size, d)
         self.folded_layers = 0
         last = len(self.layers) - 1
+        # 8-bit decode mode: only a decode row (a cached step behind the prefill) streams the copies, never a short prefill or a cache-free pass
+        w8_row = self.w8 is not None and kv_cache is not None and pos0 > 0 and B * S <= 8
         for i, lw in enumerate(self.layers):
             folded = fold and "qkv_rope_f" in lw
-            q5 = self._qkv(lw, x, S, pos0, folded).unflatten(0, (B, S)).unflatten(2, (3, H, D))
+            q8 = self.w8[i] if w8_row else None
+            q5 = self._qkv(lw, x, S, pos0, folded, q8).unflatten(0, (B, S)).unflatten(2, (3, H, D))
             if kv_cache is not None:
                 kv_cache["k"][i][:, pos0:pos0 + S].copy_(q5[:, :, 1])
                 kv_cache["v"][i][:, pos0:pos0 + S].copy_(q5[:, :, 2])
@@ -411,13 +460,13 @@ class LlamaStack:
                 attn = ops.attention(q5[:, :, 0], kv_cache["k"][i][:, :pos0 + 1], kv_cache["v"][i][:, :pos0 + 1], causal=False)
             else:
                 attn = ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], causal=True, key_valid=key_valid)
-            x = self._lin(attn.view(B * S, d), lw["o"], residual=x)
+            x = self._lin(lw, "o", attn.view(B * S, d), q8, residual=x)
             # (tests / parity only: the layer's own gate input, copied before the combine writes the MLP output into the residual stream — the
             #  layer-local routing check of oracle/parity.py recomputes the gate from it)
             x_gate_in = x.clone() if (collect_routing and i in self.moe_layers) else None
             h, gate, rstd = self._post_attention_norm(i, lw, x, folded)
             # (the last layer's row set goes to _mlp whatever produced the gate: only the top-1 gather / scatter branch prunes, a dense layer ignores it)
-            x, l_aux, r = self._mlp(i, lw, h, x, gate=gate, needed=needed if i == last else None, rstd=rstd)
+            x, l_aux, r = self._mlp(i, lw, h, x, gate=gate, needed=needed if i == last else None, rstd=rstd, q8=q8)
             if l_aux is not None:
                 aux.append(l_aux)
                 if collect_routing:
@@ -448,24 +497,27 @@ class LlamaStack:
         H, D, E, k = cfg.num_attention_heads, cfg.head_dim, cfg.num_experts, cfg.top_k_experts
         x = emb.reshape(B, d)
         self.gate_pass += 1
-        fold = ops.gemv_rmsnorm_ok(B, d, head_dim=D, swiglu_n=2 * cfg.intermediate_size)   # input_layernorm inside the qkv GEMV (same bits, one launch less per layer)
+        # input_layernorm inside the qkv GEMV (same bits, one launch less per layer); the norm-folded launches have no 8-bit twins: 8-bit mode
+        # takes the unfused branches
+        fold = self.w8 is None and ops.gemv_rmsnorm_ok(B, d, head_dim=D, swiglu_n=2 * cfg.intermediate_size)
         for i, lw in enumerate(self.layers):
+            q8 = self.w8[i] if self.w8 is not None else None
             if fold:                                            # norm + projection + RoPE + cache append: one launch, the three launches' bits
                 qkv = ops.gemv_rmsnorm_rope_append(x, lw["ln1"], cfg.rms_norm_eps, lw["qkv"], self.cos, self.sin, kv_cache["k"][i],
                                                    kv_cache["v"][i], counters[0:1], H, D, err=kv_cache["err"])
             else:
-                qkv = ops.gemv(ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps), lw["qkv"])
+                qkv = self._row_proj(lw, "qkv", ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps), q8)
                 ops.decode_rope_append(qkv, self.cos, self.sin, kv_cache["k"][i], kv_cache["v"][i], counters[0:1], H, D, err=kv_cache["err"])
             q4 = qkv.view(B, 1, 3, H, D)[:, :, 0]
             attn = ops.attention(q4, kv_cache["k"][i], kv_cache["v"][i], causal=False, sk_dev=counters[1:2])
-            x = ops.gemv(attn.view(B, d), lw["o"], residual=x)
+            x = self._row_proj(lw, "o", attn.view(B, d), q8, residual=x)
             # post-attention norm + gate + routing in ONE launch, then the expert GEMVs of _mlp's decode-row branches (the separate kernels' bits)
             if i in self.moe_layers and self.fuse_decode_routing and self._expert_gemv_rows(B) and k in (1, 2):
                 cap = self.capacity(B)
                 if k == 1:
                     draws = None if cap >= B else self._gate_draws(i, B, E, False, pass_dev)
                     h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
-                    x = self._expert_gemvs_top1(lw, h, x, expert, slot, weight)
+                    x = self._expert_gemvs_top1(lw, h, x, expert, slot, weight, q8)
                 else:
                     draws = self._gate_draws(i, B, E, True, pass_dev)
                     h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route_top2(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
@@ -475,7 +527,7 @@ class LlamaStack:
                 act = ops.gemv_rmsnorm(x, lw["ln2"], cfg.rms_norm_eps, lw["gu"], act=ops.ACT_SWIGLU_PAIR)
                 x = ops.gemv(act, lw["down"], residual=x)
             else:
-                x, _, _ = self._mlp(i, lw, ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps), x, pass_dev=pass_dev)
+                x, _, _ = self._mlp(i, lw, ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps), x, pass_dev=pass_dev, q8=q8)
         return ops.rmsnorm(x, self.norm_w, cfg.rms_norm_eps).view(B, 1, d)
 
     def next_token_logits(self, hidden_row):

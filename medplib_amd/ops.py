@@ -329,6 +329,34 @@ def gemv(x, w, bias=None, residual=None, act=ACT_NONE, out_dtype=torch.bfloat16,
     return out
 
 
+def quantize_rows_w8(w):
+    """Row-wise absmax 8-bit copy of a projection (bitsandbytes' weight format): w [N, K] or [E, N, K] bf16 -> (codes int8 of w's shape,
+    scale fp32 [N] or [E, N]) with scale = absmax / 127 and codes = rint(w * (127 / absmax)) per output row; a zero row gets scale 0."""
+    _chk(w, torch.bfloat16, "quantize_rows_w8.w")
+    assert w.is_contiguous() and w.dim() in (2, 3)
+    K = w.shape[-1]
+    codes = torch.empty(w.shape, dtype=torch.int8, device=w.device)
+    scale = torch.empty(w.shape[:-1], dtype=torch.float32, device=w.device)
+    lib().call("mp_quantize_rows_w8_bf16", _p(w), K, w.numel() // K, K, _p(codes), K, _p(scale), _stream())
+    return codes, scale
+
+
+def gemv_w8(x, codes, scale, bias=None, residual=None, act=ACT_NONE, out_dtype=torch.bfloat16, alpha=1.0, w_index=None, row_scale=None,
+            row_keep=None):
+    """gemv() on the 8-bit copy of w (quantize_rows_w8): scale[n] * (x . codes[n]) in fp32, then gemv's epilogues.  x [M <= 8, K] bf16;
+    codes [N, K] int8 with scale [N], or with w_index [E, N, K] and [E, N].  Only ACT_NONE / ACT_SWIGLU_PAIR and no bias (the library
+    refuses the rest); a row with row_keep[m] < 0 streams no weights."""
+    _chk(x, torch.bfloat16, "gemv_w8.x"); _chk(codes, torch.int8, "gemv_w8.codes"); _chk(scale, torch.float32, "gemv_w8.scale")
+    M, K = x.shape
+    N = codes.shape[-2]
+    assert x.stride(1) == 1 and codes.stride(-1) == 1 and scale.is_contiguous() and scale.shape == codes.shape[:-1]
+    out = torch.empty((M, N // 2 if act == ACT_SWIGLU_PAIR else N), dtype=out_dtype, device=x.device)
+    lib().call("mp_gemv_w8_bf16", _p(x), x.stride(0), _p(codes), codes.stride(-2), codes.stride(0) if codes.dim() == 3 else 0, _p(scale),
+               N if codes.dim() == 3 else 0, _p(out), out.stride(0), _p(bias), _p(residual), residual.stride(0) if residual is not None else 0,
+               _p(w_index), _p(row_scale), _p(row_keep), M, N, K, act, _dt(out_dtype), float(alpha), _stream())
+    return out
+
+
 def gemm_batched(a, w, out, m_dev=None, bias=None, act=ACT_NONE):
     """a [E,M,K], w [E,N,K], out [E,M,N] (bf16 or f32); m_dev int32 [E] device row counts."""
     _chk(a, torch.bfloat16, "gemm_batched.a"); _chk(w, torch.bfloat16, "gemm_batched.w")

@@ -20,7 +20,10 @@ Out of scope: the HTTP server (FastAPI / uvicorn), the controller registration, 
 --limit-model-concurrency is parsed and carried for a server built around `ModelWorker.generate_stream_gate`.
 
 `images` / `region_masks` of a request: base64 strings as the reference's clients send them (decoded with Pillow, which is imported only then)
-or uint8 arrays ([H, W, 3] RGB, [H, W]).  `FLAG_TABLE` holds the reference's command line as data; additions of this build: --precision, --apply-top-p."""
+or uint8 arrays ([H, W, 3] RGB, [H, W]).  --load-8bit (reference :72,100,642 -> builder.py:39, bitsandbytes) is a SPEED mode here, not a memory mode:
+`MedPLIBForCausalLM.enable_decode_8bit` adds int8 copies of the decoder projections in bitsandbytes' row-wise absmax format and every decode
+step streams them (half the bytes per token); the bf16 weights stay for the prefill, the activations stay bf16 and lm_head is not quantised.
+--load-4bit, --load-fp16 and any --precision but bf16 stay refused.  `FLAG_TABLE` holds the reference's command line as data; additions of this build: --precision, --apply-top-p."""
 import argparse
 import base64
 import io
@@ -69,13 +72,15 @@ def parse_args(argv):
 
 
 def check_placement(args):
-    """This build computes in bf16 on the GPU: every other --precision / --device_map (the reference's default is 'cpu') and the
-    quantised / fp16 loads are refused, like --cpu_only in the eval walk."""
+    """This build computes in bf16 on the GPU: every other --precision / --device_map (the reference's default is 'cpu') and the 4-bit /
+    fp16 loads are refused, like --cpu_only in the eval walk.  --load-8bit passes: the decode steps then stream 8-bit weight copies
+    (ModelWorker.__init__)."""
     if args.device_map != "cuda":
         raise NotImplementedError(f"--device_map {args.device_map}: this build has no CPU path (the HIP library is the only implementation); "
                                   "pass --device_map cuda")
-    if args.precision != "bf16" or args.load_8bit or args.load_4bit or args.load_fp16:
-        raise ValueError("this build computes in bf16 (the worker's own precision): --precision bf16, no --load-8bit / --load-4bit / --load-fp16")
+    if args.precision != "bf16" or args.load_4bit or args.load_fp16:
+        raise ValueError("this build computes in bf16 (the worker's own precision): --precision bf16, no --load-4bit / --load-fp16 "
+                         "(--load-8bit: 8-bit weight copies for the decode steps, activations in bf16)")
 
 
 def open_model(args, tokenizer=None):
@@ -113,6 +118,8 @@ class ModelWorker:
         check_placement(args)
         self.model, self.tokenizer, self.args = model, tokenizer, args
         self.device = model.device_
+        if args.load_8bit:                                      # (refused with NotImplementedError where the mode is not built: top-2, adapters, ...)
+            model.enable_decode_8bit(True)
         name = args.model_name
         if name is None:                                        # the last path component, or the last two under a checkpoint-N directory
             parts = args.model_path.rstrip("/").split("/")

@@ -21,6 +21,7 @@ ap.add_argument("--new", type=int, default=16)
 ap.add_argument("--kinds", default="dense,top1")
 ap.add_argument("--beams", default="1,2,4,8")
 ap.add_argument("--out", default="")
+ap.add_argument("--w8", action="store_true", help="8-bit decode weights on (enable_decode_8bit) for the model steps")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 res = {"protocol": f"slope between {args.new} and {4 * args.new} generated tokens, fastest of 3 calls each, eos off", "steps": {}, "kernels": {}}
@@ -67,6 +68,8 @@ for kind in args.kinds.split(","):
     dense = kind == "dense"
     cfg = MedPLIBConfig.medplib_7b(moe_enable=False) if dense else MedPLIBConfig.medplib_7b(moe_enable=True, num_experts=2, top_k_experts=1)
     model = (LISAForCausalLM if dense else MedPLIBForCausalLM)(cfg, device=dev).eval()
+    if args.w8:
+        model.enable_decode_8bit(True)
     L, V = 64, cfg.vocab_size
     ids = torch.randint(3, 31999, (1, L), generator=g)
     ids[0, 0] = 1; ids[0, 34], ids[0, 35], ids[0, 36] = V - 2, -200, V - 1

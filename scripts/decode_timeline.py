@@ -1,6 +1,8 @@
 """Per-position timeline of a decode layer from a rocprofv3 --kernel-trace rocpd database: the dispatches of the replayed decode graph in
 start order, folded by their position inside the layer (the launch sequence repeats every layer and every token): average duration per
-position, average gap to the next dispatch.  python scripts/decode_timeline.py <db> <out.md>"""
+position, average gap to the next dispatch.  python scripts/decode_timeline.py <db> <out.md> [marker]
+marker: the start of the name of a kernel that is launched once per layer; the layer is folded from there (default: the norm-folded qkv GEMV,
+the bf16 layer's first launch; an 8-bit layer has none: pass decode_rope_append_kernel)."""
 import re
 import sqlite3
 import sys
@@ -13,12 +15,12 @@ def short(n):
     return n.split("(")[0][:60]
 
 
-def main(db_path, out):
+def main(db_path, out, marker="gemv_rmsnorm_rope_kernel"):
     db = sqlite3.connect(db_path)
     rows = list(db.execute("select name, start, end, grid_x, workgroup_x from kernels order by start"))
     names = [short(r[0]) for r in rows]
-    # the layer's first launch: the norm-folded qkv GEMV
-    first = [i for i, n in enumerate(names) if n.startswith("gemv_rmsnorm_rope_kernel")]
+    # the layer's first launch: the norm-folded qkv GEMV (or the caller's marker)
+    first = [i for i, n in enumerate(names) if n.startswith(marker)]
     if len(first) < 64:
         print("no decode layers found"); return
     period = first[1] - first[0]
@@ -46,4 +48,4 @@ def main(db_path, out):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2])
+    main(*sys.argv[1:4])
