@@ -17,7 +17,7 @@ struct GemvArgs {
   const float* bias; const bf16_t* residual; int64_t ldr;
   const int* w_index;        // [M] device: weight matrix per row (null = one shared matrix)
   const float* row_scale;    // [M] device or null
-  const int* row_keep;       // [M] device or null: rows with row_keep[m] < 0 get scale 0 (capacity-dropped tokens)
+  const int* row_keep;       // [M] device or null: rows with row_keep[m] < 0 are capacity-dropped tokens (gv_store_dropped)
   int M, N, K, act, out_f32;
   float alpha;
 };
@@ -143,7 +143,9 @@ __device__ __forceinline__ void gv_indexed_row_dot(const bf16_t* __restrict__ xr
   for (int r = 0; r < 4; ++r) acc[r] = wave_sum(acc[r]);
 }
 
-// INDEXED: every row picks its own weight matrix (MoE experts); rows are processed one after the other
+// INDEXED: every row picks its own weight matrix (MoE experts); rows are processed one after the other.  A capacity-dropped row
+// (row_keep[m] < 0) still streams its weights here.  The plain form then stores what the int8 kernel stores, the residual's bits (+0
+// without one); the SwiGLU form WRITES the row (its expert's SwiGLU, which no caller reads) where the int8 kernel leaves it unwritten.
 template <bool SWIGLU>
 __global__ __launch_bounds__(256) void gemv_indexed_kernel(GemvArgs g) {
   const int lane = threadIdx.x & 63;
@@ -165,7 +167,10 @@ __global__ __launch_bounds__(256) void gemv_indexed_kernel(GemvArgs g) {
     } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (rows[r] < g.N) gv_store_indexed(g, m, rows[r], acc[r], scale);
+        if (rows[r] < g.N) {
+          if (gv_row_dropped(g, m)) gv_store_dropped(g, m, rows[r]);
+          else gv_store_indexed(g, m, rows[r], acc[r], scale);
+        }
     }
   }
 }
@@ -519,7 +524,8 @@ __global__ __launch_bounds__(1024) void gemv_ksplit_kernel(GemvArgs g) {
     const int n = row0 + lane;                               // lane r of the kp = 0 wave finishes row r of its group
     if (n >= g.N) continue;
     const float a = ((red[0][rg][lane] + red[1][rg][lane]) + red[2][rg][lane]) + red[3][rg][lane];
-    if (g.w_index) gv_store_indexed(g, m, n, a, gv_row_scale(g, m));      // gemv_indexed_kernel's epilogue
+    if (g.w_index && gv_row_dropped(g, m)) gv_store_dropped(g, m, n);
+    else if (g.w_index) gv_store_indexed(g, m, n, a, gv_row_scale(g, m)); // gemv_indexed_kernel's epilogue
     else gv_store_shared(g, m, n, a);                                      // gemv_shared_kernel's
   }
 }

@@ -39,6 +39,16 @@ __device__ __forceinline__ void gv_store_indexed(const Args& g, int m, int n, fl
   reinterpret_cast<bf16_t*>(g.y)[(int64_t)m * g.ldy + n] = (bf16_t)v;
 }
 
+// a capacity-dropped row of the indexed form: what scale 0 leaves of the combine, the residual's own bits (+0 without one).  Stored as such and
+// not as 0 * bf16(a) + residual, which is -0 for a negative a without a residual (and NaN for a non-finite a)
+template <class Args>
+__device__ __forceinline__ void gv_store_dropped(const Args& g, int m, int n) {
+  reinterpret_cast<bf16_t*>(g.y)[(int64_t)m * g.ldy + n] = g.residual ? g.residual[(int64_t)m * g.ldr + n] : (bf16_t)0.f;
+}
+
+template <class Args>
+__device__ __forceinline__ bool gv_row_dropped(const Args& g, int m) { return g.row_keep && g.row_keep[m] < 0; }
+
 // the combine weight of row m in the indexed form: row_scale[m] (1 without), 0 for a capacity-dropped row
 template <class Args>
 __device__ __forceinline__ float gv_row_scale(const Args& g, int m) {

@@ -86,11 +86,6 @@ __device__ __forceinline__ void gq_stream(const bf16_t* __restrict__ x, int64_t 
   }
 }
 
-// a capacity-dropped row of the indexed form: what scale 0 leaves of the combine, the residual's own bits (0 without one), and no weight read
-__device__ __forceinline__ void gq_store_dropped(const GemvW8Args& g, int m, int n) {
-  reinterpret_cast<bf16_t*>(g.y)[(int64_t)m * g.ldy + n] = g.residual ? g.residual[(int64_t)m * g.ldr + n] : (bf16_t)0.f;
-}
-
 // SHARED: all M rows use the same W (the codes are loaded once and reused for every x row)
 template <int M, bool SWIGLU>
 __global__ __launch_bounds__(256) void gemv_w8_shared_kernel(GemvW8Args g) {
@@ -141,7 +136,7 @@ __global__ __launch_bounds__(256) void gemv_w8_indexed_kernel(GemvW8Args g) {
   if (rows[0] >= g.N) return;
   for (int m = 0; m < g.M; ++m) {
     if (g.row_keep && g.row_keep[m] < 0) {
-      if (!SWIGLU && lane < 4 && wid * 4 + lane < g.N) gq_store_dropped(g, m, wid * 4 + lane);
+      if (!SWIGLU && lane < 4 && wid * 4 + lane < g.N) gv_store_dropped(g, m, wid * 4 + lane);
       continue;
     }
     const int e = g.w_index[m];
@@ -181,7 +176,7 @@ __global__ __launch_bounds__(1024) void gemv_w8_ksplit_kernel(GemvW8Args g) {
   for (int m = 0; m < g.M; ++m) {
     const int e = g.w_index ? g.w_index[m] : 0;
     if (g.w_index && g.row_keep && g.row_keep[m] < 0) {     // (uniform over the workgroup)
-      if (fin) gq_store_dropped(g, m, n);
+      if (fin) gv_store_dropped(g, m, n);
       continue;
     }
     const int8_t* Wm = g.W + (int64_t)e * g.strideW;
