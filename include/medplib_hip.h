@@ -110,8 +110,8 @@ int mp_gemm_bf16_nt_batched_rows(const void* A, int64_t lda, int64_t strideA, co
 /* y[m, n] = epilogue(x[m, :] . W[n, :]) for M <= 8 rows: the single-token decode steps of evaluate() (HF generate with a KV cache,
  * MedPLIB.py:592-606), bound by the HBM stream of W.  Same epilogues as mp_gemm_bf16_nt (incl. SWIGLU_PAIR).
  * MoE decode: w_index[m] (device int) picks the expert's matrix (W + w_index[m] * strideW) per row; then the output is
- * residual + row_scale[m] * bf16(acc); a row whose row_keep[m] < 0 (a capacity-dropped token) is the residual's own bits, +0 without
- * one (the SWIGLU_PAIR form writes such a row, with values nobody reads). */
+ * residual + row_scale[m] * bf16(acc); a row whose row_keep[m] < 0 (a capacity-dropped token) streams no weights and is the residual's
+ * own bits, +0 without one (the SWIGLU_PAIR form leaves such a row unwritten). */
 int mp_gemv_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy, const float* bias,
                  const void* residual, int64_t ldr, const int* w_index, const float* row_scale, const int* row_keep, int M, int N, int K,
                  int act, int out_dtype, float alpha, hipStream_t stream);

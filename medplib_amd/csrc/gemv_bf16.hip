@@ -1,179 +1,16 @@
 // bf16 GEMV for the single-token decode steps of evaluate() (HF generate with a KV cache, MedPLIB.py:592-606): y[m, n] = x[m, :] . W[n, :]
-// for M <= 8 rows.  One decode step reads every LLM weight once, so this kernel is bound by the HBM stream of W (13.2 GB per
-// token at 7B): a wave owns four consecutive output columns (four W rows of K bf16), streams them with 16-byte loads — eight in
-// flight per lane — against the x chunk it holds in registers, reduces across the wave, and applies the same fused epilogues as the
-// GEMM (bias, activation, residual, SwiGLU pairing over the interleaved gate|up rows).  MoE decode: `w_index[m]` (device) selects
-// the expert's weight matrix per row and `row_scale[m]` / `row_keep[m]` carry the top-1 gate probability and the capacity drop.
-#include "gemv_epilogue.h"
+// for M <= 8 rows.  One decode step reads every LLM weight once, so these kernels are bound by the HBM stream of W (13.2 GB per token at 7B).
+// mp_gemv_bf16 is the bf16 policy of the three forms of gemv_forms.h (shared, indexed, K-split: the kernels, the weight streams and the host
+// dispatch live there, under the int8 entry point of gemv_w8.hip too).  What is written here: the norm-folded GEMVs (RMSNorm in front of the
+// projection, RoPE + the KV-cache append behind it) and the top-2 MoE pair, which call the same streams.  MoE decode: `w_index[m]` (device)
+// selects the expert's weight matrix per row and `row_scale[m]` / `row_keep[m]` carry the top-1 gate probability and the capacity drop.
+#include "gemv_forms.h"
 
 namespace {
 
-constexpr int GV_MAXM = 8;
-
-struct GemvArgs {
-  const bf16_t* x; int64_t ldx;
-  const bf16_t* W; int64_t ldw; int64_t strideW;
-  void* y; int64_t ldy;
-  const float* bias; const bf16_t* residual; int64_t ldr;
-  const int* w_index;        // [M] device: weight matrix per row (null = one shared matrix)
-  const float* row_scale;    // [M] device or null
-  const int* row_keep;       // [M] device or null: rows with row_keep[m] < 0 are capacity-dropped tokens (gv_store_dropped)
-  int M, N, K, act, out_f32;
-  float alpha;
-};
-
-// The weight stream: every byte is read once per token by ONE wave, so the loads are marked non-temporal (streaming lines do not displace
-// the x rows, norm weights and KV cache other kernels of the decode step re-read from L2; MP_GEMV_NT=0 at build time restores the default
-// policy for an A/B).
-#ifndef MP_GEMV_NT
-#define MP_GEMV_NT 1
-#endif
 #ifndef MP_GEMV_PIPE
 #define MP_GEMV_PIPE 1        // 0 at build time: the norm-folded GEMVs request a trip only after the previous one was consumed (round 4; A/B)
 #endif
-__device__ __forceinline__ bf16x8 gv_ldw(const bf16_t* p) {
-#if MP_GEMV_NT
-  return __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p));
-#else
-  return *reinterpret_cast<const bf16x8*>(p);
-#endif
-}
-
-__device__ __forceinline__ float gv_dot8(const bf16x8 a, const bf16x8 b, float acc) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc = fmaf((float)a[j], (float)b[j], acc);
-  return acc;
-}
-
-// SHARED: all M rows use the same W (W rows are loaded once and reused for every x row)
-template <int M, bool SWIGLU>
-__global__ __launch_bounds__(256) void gemv_shared_kernel(GemvArgs g) {
-  const int lane = threadIdx.x & 63;
-  const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
-  int rows[4];
-  gv_wave_rows<SWIGLU>(wid, rows);                          // plain: 4 consecutive columns; SWIGLU: two gate rows and their up rows
-  if (rows[0] >= g.N) return;
-  const bf16_t* wp[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) wp[r] = g.W + (int64_t)min(rows[r], g.N - 1) * g.ldw;
-  float acc[M][4];
-#pragma unroll
-  for (int m = 0; m < M; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[m][r] = 0.f;
-  const int iters = g.K / 512;                              // 64 lanes x 8 elements per step
-  int k = lane * 8;
-  // (four steps per trip for the one-row case, 16 loads in flight, was measured too: o_proj 11.0 -> 11.2 us — no change)
-  int it = 0;
-  for (; it + 1 < iters; it += 2, k += 1024) {              // two steps per trip: 8 weight loads in flight per lane
-    bf16x8 w0[4], w1[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { w0[r] = gv_ldw(wp[r] + k); w1[r] = gv_ldw(wp[r] + k + 512); }
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(g.x + (int64_t)m * g.ldx + k);
-      const bf16x8 x1 = *reinterpret_cast<const bf16x8*>(g.x + (int64_t)m * g.ldx + k + 512);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[m][r] = gv_dot8(x1, w1[r], gv_dot8(x0, w0[r], acc[m][r]));
-    }
-  }
-  if (it < iters) {
-    bf16x8 w0[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) w0[r] = gv_ldw(wp[r] + k);
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(g.x + (int64_t)m * g.ldx + k);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[m][r] = gv_dot8(x0, w0[r], acc[m][r]);
-    }
-  }
-  k = iters * 512 + lane * 8;                                // K tail (K % 512 != 0; K % 8 == 0)
-  if (k < g.K) {
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(g.x + (int64_t)m * g.ldx + k);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[m][r] = gv_dot8(x0, gv_ldw(wp[r] + k), acc[m][r]);
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < M; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[m][r] = wave_sum(acc[m][r]);
-  if (lane != 0) return;
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    if (SWIGLU) {
-      gv_swiglu_store(acc[m], rows, g.N, g.alpha, reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (rows[r] < g.N) gv_store_shared(g, m, rows[r], acc[m][r]);
-    }
-  }
-}
-
-// One row of the indexed (expert) form: the wave's four W rows against x row xr, four 512-element steps per trip (16 weight loads in
-// flight per lane: one step per trip left every trip waiting on its own 4 loads — the down projection's 21.5 trips per row were 21.5
-// dependent round trips), then the wave reduction.  acc[r] = x . W[row r].
-__device__ __forceinline__ void gv_indexed_row_dot(const bf16_t* __restrict__ xr, const bf16_t* const (&wp)[4], int K, int lane, float (&acc)[4]) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = 0.f;
-  int k = lane * 8;
-  for (; k + 3 * 512 < K; k += 4 * 512) {
-    bf16x8 xs[4], ws[4][4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      xs[u] = *reinterpret_cast<const bf16x8*>(xr + k + u * 512);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ws[u][r] = gv_ldw(wp[r] + k + u * 512);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(xs[u], ws[u][r], acc[r]);
-  }
-  for (; k < K; k += 512) {
-    const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(xr + k);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(x0, gv_ldw(wp[r] + k), acc[r]);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = wave_sum(acc[r]);
-}
-
-// INDEXED: every row picks its own weight matrix (MoE experts); rows are processed one after the other.  A capacity-dropped row
-// (row_keep[m] < 0) still streams its weights here.  The plain form then stores what the int8 kernel stores, the residual's bits (+0
-// without one); the SwiGLU form WRITES the row (its expert's SwiGLU, which no caller reads) where the int8 kernel leaves it unwritten.
-template <bool SWIGLU>
-__global__ __launch_bounds__(256) void gemv_indexed_kernel(GemvArgs g) {
-  const int lane = threadIdx.x & 63;
-  const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
-  int rows[4];
-  gv_wave_rows<SWIGLU>(wid, rows);
-  if (rows[0] >= g.N) return;
-  for (int m = 0; m < g.M; ++m) {
-    const bf16_t* Wm = g.W + (int64_t)g.w_index[m] * g.strideW;
-    const float scale = gv_row_scale(g, m);
-    const bf16_t* wp[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(rows[r], g.N - 1) * g.ldw;
-    float acc[4];
-    gv_indexed_row_dot(g.x + (int64_t)m * g.ldx, wp, g.K, lane, acc);
-    if (lane != 0) continue;
-    if (SWIGLU) {
-      gv_swiglu_store(acc, rows, g.N, 1.f, reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (rows[r] < g.N) {
-          if (gv_row_dropped(g, m)) gv_store_dropped(g, m, rows[r]);
-          else gv_store_indexed(g, m, rows[r], acc[r], scale);
-        }
-    }
-  }
-}
 
 // The shared core of the norm-folded GEMVs: every wave normalises the M rows (HF rounding points, rmsnorm_bf16_kernel's summation order),
 // parks them in its own LDS region and streams its four weight rows against them in a RUNTIME loop, two steps per trip (8 weight loads in
@@ -466,81 +303,16 @@ __global__ __launch_bounds__(256) void gemv_rmsnorm_rope_kernel(GemvArgs g, cons
   }
 }
 
-// K-SPLIT form for the narrow projections of a decode step (N <= 4096: o_proj and the down projections, one row of x or the indexed
-// expert form).  With a wave per four W rows those launches are 256 workgroups of four waves — one wave per SIMD, 8-16 KB of loads in
-// flight per wave and nothing to hide their latency behind: the o projection streamed at 3.2 TB/s, the expert down projection at 4.2
-// (gate|up, 1376 workgroups: 5.9).  Here a workgroup of SIXTEEN waves owns the same sixteen W rows: wave (rg, kp) takes the four rows
-// of row group rg and the 512-element steps s = kp, kp + 4, kp + 8, ... of K, so a CU has four times the loads in flight and four waves
-// per SIMD; the four K parts of a row are added in ascending kp order through LDS (a fixed order: deterministic, but not the
-// single-wave order of gemv_shared_kernel — the two forms agree to fp32 rounding, not bit for bit).
-// Round 5, measured and dropped: the same kernel with EVERY weight load of a row requested before the first multiply (five steps of 4 x 16
-// bytes per lane up front, the x row through LDS; a CU's 352 KB share of the down projection fits its register file): 21.4 us against this
-// form's 18.8 on the 90 MB down projection, bit-identical.  A launch here is ~4 us of fixed cost (dispatch, first latency, reduction,
-// epilogue) + bytes / 6.3 TB/s — qkv 16.0 + 3.3, o 5.3 + 3.9, gate|up 28.6 + 1.9, down 14.3 + 4.5 (profiles/r05a_decode_timeline_dense.md) —
-// and the eight loads per lane it keeps in flight already cover the latency; deeper queues only lengthen the register-file fill.
-// K part kp (0..3) of one row in the K-split form: the 512-element steps s = kp, kp + 4, ... against the wave's four W rows, two of
-// them per trip (8 weight loads in flight per lane), then the wave reduction.  acc[r] = this part's share of x . W[row r].
-__device__ __forceinline__ void gv_ksplit_part_dot(const bf16_t* __restrict__ xr, const bf16_t* const (&wp)[4], int K, int lane, int kp,
-                                                   float (&acc)[4]) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = 0.f;
-  int k = lane * 8 + kp * 512;
-  for (; k + 2048 < K; k += 4096) {
-    const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(xr + k), x1 = *reinterpret_cast<const bf16x8*>(xr + k + 2048);
-    bf16x8 w0[4], w1[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { w0[r] = gv_ldw(wp[r] + k); w1[r] = gv_ldw(wp[r] + k + 2048); }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(x1, w1[r], gv_dot8(x0, w0[r], acc[r]));
-  }
-  if (k < K) {
-    const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(xr + k);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = gv_dot8(x0, gv_ldw(wp[r] + k), acc[r]);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = wave_sum(acc[r]);
-}
-
-__global__ __launch_bounds__(1024) void gemv_ksplit_kernel(GemvArgs g) {
-  __shared__ float red[4][4][4];                            // [kp][rg][r]
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int rg = wv & 3, kp = wv >> 2;
-  const int row0 = (blockIdx.x * 4 + rg) * 4;
-  for (int m = 0; m < g.M; ++m) {
-    const bf16_t* Wm = g.W + (g.w_index ? (int64_t)g.w_index[m] * g.strideW : 0);
-    const bf16_t* wp[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(row0 + r, g.N - 1) * g.ldw;
-    float acc[4];
-    gv_ksplit_part_dot(g.x + (int64_t)m * g.ldx, wp, g.K, lane, kp, acc);
-    if (m > 0) __syncthreads();                             // the previous row's partials have been read
-    if (lane == 0) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[kp][rg][r] = acc[r];
-    }
-    __syncthreads();
-    if (kp != 0 || lane >= 4) continue;
-    const int n = row0 + lane;                               // lane r of the kp = 0 wave finishes row r of its group
-    if (n >= g.N) continue;
-    const float a = ((red[0][rg][lane] + red[1][rg][lane]) + red[2][rg][lane]) + red[3][rg][lane];
-    if (g.w_index && gv_row_dropped(g, m)) gv_store_dropped(g, m, n);
-    else if (g.w_index) gv_store_indexed(g, m, n, a, gv_row_scale(g, m)); // gemv_indexed_kernel's epilogue
-    else gv_store_shared(g, m, n, a);                                      // gemv_shared_kernel's
-  }
-}
-
 // ---------------- top-2 MoE decode: the two expert GEMVs of 2T (token, choice) entries ----------------
 // Entry layout of mp_moe_route_top2: entry e = c * T + t is choice c (0 = first, 1 = second) of token t, with expert index w_index[e],
 // slot row_keep[e] (< 0: dropped by the capacity limit) and combine weight row_scale[e].
-// gate|up: act[e] = SwiGLU(x[t] . W[w_index[e]]) — gemv_indexed_kernel<true>'s arithmetic per entry, x row e % T.  A dropped entry
-// streams no weights and its act row is not written (the down projection never reads it).
+// gate|up: act[e] = SwiGLU(x[t] . W[w_index[e]]) — the arithmetic of gemv_indexed_kernel's SwiGLU form per entry, x row e % T.  A dropped
+// entry streams no weights and its act row is not written (the down projection never reads it).
 __global__ __launch_bounds__(256) void gemv_top2_gate_up_kernel(GemvArgs g, int T) {
   const int lane = threadIdx.x & 63;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int pair = wid * 2;
-  const int blk = pair >> 5, j = pair & 31;
-  const int rows[4] = {blk * 64 + j, blk * 64 + j + 1, blk * 64 + j + 32, blk * 64 + j + 33};
+  int rows[4];
+  gv_wave_rows<true>(wid, rows);
   if (rows[0] >= g.N) return;
   for (int e = 0; e < 2 * T; ++e) {
     if (g.row_keep[e] < 0) continue;
@@ -549,7 +321,7 @@ __global__ __launch_bounds__(256) void gemv_top2_gate_up_kernel(GemvArgs g, int 
 #pragma unroll
     for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(rows[r], g.N - 1) * g.ldw;
     float acc[4];
-    gv_indexed_row_dot(g.x + (int64_t)(e % T) * g.ldx, wp, g.K, lane, acc);
+    WeightBf16::row_dot(g.x + (int64_t)(e % T) * g.ldx, wp, g.K, lane, acc);
     if (lane == 0) gv_swiglu_store(acc, rows, g.N, 1.f, reinterpret_cast<bf16_t*>(g.y) + (int64_t)e * g.ldy);
   }
 }
@@ -558,12 +330,8 @@ __global__ __launch_bounds__(256) void gemv_top2_gate_up_kernel(GemvArgs g, int 
 // the kept choices c = 0, 1 in that order — mp_moe_combine_bf16's summation order and rounding points, on expert outputs computed as
 // gemv_ksplit_kernel computes them (sixteen waves per sixteen rows, K split four ways, the parts added in ascending order).  One launch.
 __global__ __launch_bounds__(1024) void gemv_top2_down_kernel(GemvArgs g, int T) {
-  __shared__ float red[4][4][4];                            // [kp][rg][r]
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int rg = wv & 3, kp = wv >> 2;
-  const int row0 = (blockIdx.x * 4 + rg) * 4;
-  const int n = row0 + lane;                                // (lane r of the kp = 0 wave finishes row r of its group)
-  const bool fin = kp == 0 && lane < 4 && n < g.N;
+  __shared__ float red[4][4][4];
+  KsplitWave w(g.N);
   for (int t = 0; t < T; ++t) {
     float y[2] = {0.f, 0.f};
     for (int c = 0; c < 2; ++c) {
@@ -572,18 +340,12 @@ __global__ __launch_bounds__(1024) void gemv_top2_down_kernel(GemvArgs g, int T)
       const bf16_t* Wm = g.W + (int64_t)g.w_index[e] * g.strideW;
       const bf16_t* wp[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(row0 + r, g.N - 1) * g.ldw;
+      for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(w.row0 + r, g.N - 1) * g.ldw;
       float acc[4];
-      gv_ksplit_part_dot(g.x + (int64_t)e * g.ldx, wp, g.K, lane, kp, acc);
-      __syncthreads();                                      // the previous entry's partials have been read
-      if (lane == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[kp][rg][r] = acc[r];
-      }
-      __syncthreads();
-      if (fin) y[c] = (float)(bf16_t)(((red[0][rg][lane] + red[1][rg][lane]) + red[2][rg][lane]) + red[3][rg][lane]);
+      WeightBf16::part_dot(g.x + (int64_t)e * g.ldx, wp, g.K, w.lane, w.kp, acc);
+      y[c] = (float)(bf16_t)w.sum(red, acc);
     }
-    if (!fin) continue;
+    if (!w.fin) continue;
     float acc = 0.f;
     for (int c = 0; c < 2; ++c) {
       const int e = c * T + t;
@@ -591,14 +353,8 @@ __global__ __launch_bounds__(1024) void gemv_top2_down_kernel(GemvArgs g, int T)
       acc = fmaf(g.row_scale[e], y[c], acc);
     }
     bf16_t* yo = reinterpret_cast<bf16_t*>(g.y) + (int64_t)t * g.ldy;
-    yo[n] = g.residual ? (bf16_t)((float)g.residual[(int64_t)t * g.ldr + n] + acc) : (bf16_t)acc;
+    yo[w.n] = g.residual ? (bf16_t)((float)g.residual[(int64_t)t * g.ldr + w.n] + acc) : (bf16_t)acc;
   }
-}
-
-template <int M>
-void launch_shared(const GemvArgs& g, dim3 grid, hipStream_t s) {
-  if (g.act == ACT_SWIGLU_PAIR) hipLaunchKernelGGL((gemv_shared_kernel<M, true>), grid, dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((gemv_shared_kernel<M, false>), grid, dim3(256), 0, s, g);
 }
 
 }  // namespace
@@ -616,35 +372,8 @@ extern "C" int mp_gemv_bf16(const void* x, int64_t ldx, const void* W, int64_t l
              "mp_gemv_bf16: the indexed (expert) form takes no bias and only NONE / SWIGLU_PAIR");
   GemvArgs g{(const bf16_t*)x, ldx, (const bf16_t*)W, ldw, strideW, y, ldy, bias, (const bf16_t*)residual, ldr, w_index, row_scale, row_keep,
              M, N, K, act, out_dtype == MP_F32, alpha};
-  const int waves = act == ACT_SWIGLU_PAIR ? N / 4 : (int)mp_cdiv(N, 4);
-  const dim3 grid((unsigned)mp_cdiv(waves, 4));
-  // narrow projections with a long K (o_proj, the down projections of a decode step): sixteen waves per sixteen rows, K split four ways
-  static int ksplit = -1;
-  if (ksplit < 0) { const char* e = getenv("MP_GEMV_KSPLIT"); ksplit = (e && atoi(e) == 0) ? 0 : 1; }     // 0: the one-wave-per-four-rows kernels (A/B)
-  if (ksplit && act != ACT_SWIGLU_PAIR && N <= 4096 && K >= 4096 && (w_index || M == 1)) {
-    hipLaunchKernelGGL(gemv_ksplit_kernel, grid, dim3(1024), 0, stream, g);
-    return mp_check_launch("mp_gemv_bf16(ksplit)");
-  }
-  if (w_index) {
-    if (act == ACT_SWIGLU_PAIR) hipLaunchKernelGGL(gemv_indexed_kernel<true>, grid, dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL(gemv_indexed_kernel<false>, grid, dim3(256), 0, stream, g);
-    return mp_check_launch("mp_gemv_bf16(indexed)");
-  }
-  switch (M) {
-    case 1: launch_shared<1>(g, grid, stream); break;
-    case 2: launch_shared<2>(g, grid, stream); break;
-    case 3: launch_shared<3>(g, grid, stream); break;
-    case 4: launch_shared<4>(g, grid, stream); break;
-    default: {      // 5..8 rows: two passes of <= 4 over the same weights
-      GemvArgs a = g; a.M = 4; launch_shared<4>(a, grid, stream);
-      GemvArgs b = g; b.M = M - 4; b.x = g.x + 4 * ldx;
-      b.y = g.out_f32 ? (void*)(reinterpret_cast<float*>(y) + 4 * ldy) : (void*)(reinterpret_cast<bf16_t*>(y) + 4 * ldy);
-      if (g.residual) b.residual = g.residual + 4 * ldr;
-      switch (b.M) { case 1: launch_shared<1>(b, grid, stream); break; case 2: launch_shared<2>(b, grid, stream); break;
-                     case 3: launch_shared<3>(b, grid, stream); break; default: launch_shared<4>(b, grid, stream); }
-    }
-  }
-  return mp_check_launch("mp_gemv_bf16");
+  static const char* const names[3] = {"mp_gemv_bf16", "mp_gemv_bf16(indexed)", "mp_gemv_bf16(ksplit)"};
+  return gemv_launch<WeightBf16>(g, stream, names);
 }
 
 extern "C" int mp_gemv_top2_gate_up_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* act, int64_t ldact,

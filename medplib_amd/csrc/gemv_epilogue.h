@@ -1,6 +1,6 @@
-// The epilogues of the decode-step GEMVs, shared by the bf16 kernels (gemv_bf16.hip) and the 8-bit-weight kernels (gemv_w8.hip): what happens
-// to a finished fp32 dot product `a` of output column n of row m.  `Args` is the kernel's argument block (GemvArgs / GemvW8Args: the same field
-// names).  The rounding points are those of the 256x256 GEMM epilogue, so a decode row and a prefill row round at the same places.
+// The epilogues of the decode-step GEMVs (gemv_forms.h, gemv_bf16.hip): what happens to a finished fp32 dot product `a` of output column n of
+// row m.  `Args` is the kernel's argument block (GemvArgsT of either weight type).  The rounding points are those of the 256x256 GEMM
+// epilogue, so a decode row and a prefill row round at the same places.
 #pragma once
 #include "gemm_common.h"
 
@@ -46,16 +46,24 @@ __device__ __forceinline__ void gv_store_dropped(const Args& g, int m, int n) {
   reinterpret_cast<bf16_t*>(g.y)[(int64_t)m * g.ldy + n] = g.residual ? g.residual[(int64_t)m * g.ldr + n] : (bf16_t)0.f;
 }
 
+// row m of the indexed form: its weight matrix, and whether the capacity limit dropped it (row_keep[m] < 0).  The two loads are requested
+// together, with no branch between them (a null row_keep reads w_index[m] in its place and ignores it), so a row waits one round trip ahead
+// of its weight stream, not two.  Both arrays were written by earlier launches and m is uniform, so they are read as constant memory (scalar
+// loads in every form).  The empty asm wants both values at one point: without it the compiler moves the w_index load behind the drop
+// branch, where only the kept row uses it, and the row waits twice.
+struct GvRow { int e; bool dropped; };
 template <class Args>
-__device__ __forceinline__ bool gv_row_dropped(const Args& g, int m) { return g.row_keep && g.row_keep[m] < 0; }
-
-// the combine weight of row m in the indexed form: row_scale[m] (1 without), 0 for a capacity-dropped row
-template <class Args>
-__device__ __forceinline__ float gv_row_scale(const Args& g, int m) {
-  float scale = g.row_scale ? g.row_scale[m] : 1.f;
-  if (g.row_keep && g.row_keep[m] < 0) scale = 0.f;
-  return scale;
+__device__ __forceinline__ GvRow gv_row(const Args& g, int m) {
+  typedef const int __attribute__((address_space(4))) * const_int_ptr;
+  const int* keep = g.row_keep ? g.row_keep : g.w_index;
+  int e = ((const_int_ptr)g.w_index)[m], k = ((const_int_ptr)keep)[m];
+  asm volatile("" : "+s"(e), "+s"(k));
+  return GvRow{e, g.row_keep && k < 0};
 }
+
+// the combine weight of a kept row m in the indexed form: row_scale[m] (1 without)
+template <class Args>
+__device__ __forceinline__ float gv_row_scale(const Args& g, int m) { return g.row_scale ? g.row_scale[m] : 1.f; }
 
 // SwiGLU pairing (lane 0): gate rows {g0, g0+1} = acc[0..1] and their up rows {g0+32, g0+33} = acc[2..3] -> two output columns of yo
 __device__ __forceinline__ void gv_swiglu_store(const float (&acc)[4], const int (&rows)[4], int N, float alpha, bf16_t* __restrict__ yo) {

@@ -256,7 +256,7 @@ class LlamaStack:
         capacity drop and the residual ride in the down projection's epilogue.  Behind _mlp's routing and behind decode_step's fused one."""
         if q8 is not None:         # (the 8-bit gate|up also skips a dropped row's weights; its act row stays unwritten and the down projection never reads it)
             act = self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR, w_index=expert, row_keep=slot)
-        else:
+        else:                      # (the bf16 kernel would skip it too, given row_keep; the recorded launch traces pin this call without it)
             act = self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR, w_index=expert)
         return self._row_proj(lw, "down", act, q8, residual=x, w_index=expert, row_scale=weight, row_keep=slot)
 

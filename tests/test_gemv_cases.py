@@ -120,11 +120,14 @@ def test_references_round_where_the_epilogues_round():
 
 
 def test_route_restates_the_two_entry_points():
-    """The predicate text is in both sources, and route() is that predicate, the indexed branch, then the 4 + (M - 4) split."""
-    for name in ("gemv_bf16.hip", "gemv_w8.hip"):
-        src = open(os.path.join(ROOT, "medplib_amd", "csrc", name)).read()
-        assert re.search(r"act != ACT_SWIGLU_PAIR && N <= 4096 && K >= 4096 && \(w_index \|\| M == 1\)", src), name
-        assert "M - 4" in src
+    """The predicate text and the 4 + (M - 4) split occur once under csrc/, in the header both entry points dispatch through, and route() is
+    that predicate, the indexed branch, then the split."""
+    csrc = os.path.join(ROOT, "medplib_amd", "csrc")
+    srcs = {name: open(os.path.join(csrc, name)).read() for name in sorted(os.listdir(csrc)) if name.endswith((".h", ".hip", ".cpp"))}
+    predicate = r"act != ACT_SWIGLU_PAIR && N <= 4096 && K >= 4096 && \(w_index \|\| M == 1\)"
+    for text in (predicate, r"\.M = M - 4"):                # (the second pass of the split; anchored, so another kernel may still write "M - 4")
+        assert {name: len(re.findall(text, src)) for name, src in srcs.items() if re.search(text, src)} == {"gemv_forms.h": 1}, text
+    assert "gemv_bf16.hip" in srcs and "gemv_w8.hip" in srcs
     for w8 in (False, True):
         assert C.route(1, 4096, 4096, False, False, w8) == ("ksplit", None)
         assert C.route(1, 4097, 4096, False, False, w8) == ("shared", (1,))

@@ -87,9 +87,9 @@ def _out_arena(rows, cols, f32, dev):
     return torch.full((rows + 1, cols + 8), S32 if f32 else S16, dtype=torch.int32 if f32 else torch.int16, device=dev)
 
 
-def _take(y, rows, cols, f32, tag, unwritten=(), free=()):
+def _take(y, rows, cols, f32, tag, unwritten=()):
     """The [rows, cols] corner of an output arena after the launch.  Everything else still holds the sentinel, so do the `unwritten` rows;
-    no other row holds a NaN, except the `free` rows, whose values nobody asserts."""
+    no other row holds a NaN."""
     torch.cuda.synchronize()
     a = y.cpu()
     s = S32 if f32 else S16
@@ -100,13 +100,13 @@ def _take(y, rows, cols, f32, tag, unwritten=(), free=()):
     for m in unwritten:
         assert bool((inside[m] == s).all()), (tag, m, "a dropped row was written")
     vals = inside.view(torch.float32 if f32 else torch.bfloat16)
-    checked = [m for m in range(rows) if m not in unwritten and m not in free]
+    checked = [m for m in range(rows) if m not in unwritten]
     assert not bool(torch.isnan(vals[checked]).any()), (tag, "NaN: a guard was read or an element was not written")
     return vals
 
 
 def _gemv(dev, o, w8, act=C.ACT_NONE, f32=False, alpha=1.0, bias=False, res=False, scale=False, keep=None, x=None, idx=None,
-          unwritten=(), free=()):
+          unwritten=()):
     """One launch of mp_gemv_bf16 / mp_gemv_w8_bf16 on o's operands inside their guard bands -> y [M, N or N / 2] on the CPU."""
     x = o.x if x is None else x
     idx = getattr(o, "idx", None) if idx is None else idx
@@ -128,7 +128,7 @@ def _gemv(dev, o, w8, act=C.ACT_NONE, f32=False, alpha=1.0, bias=False, res=Fals
         _call("mp_gemv_w8_bf16", xd.data_ptr(), xd.stride(0), W.data_ptr(), ldw, strideW, sc.data_ptr(), strideScale, *tail)
     else:
         _call("mp_gemv_bf16", xd.data_ptr(), xd.stride(0), W.data_ptr(), ldw, strideW, *tail)
-    return _take(y, M, n_out, f32, tag, unwritten, free)
+    return _take(y, M, n_out, f32, tag, unwritten)
 
 
 def _dropped(keep):
@@ -228,7 +228,7 @@ def test_swiglu_forms_at_ragged_rows_and_drops(dev):
     element at 0.95 of it, gate -6.4 against up -372, where the gate's bf16 rounding ahead of SiLU is what counts) and on random operands
     of that test's distribution, for which the tolerance was set (int8: the oracle sees code * scale).  Indexed form under
     every drop pattern: kept rows are the same bits in the int8 kernel, the bf16 kernel and mp_gemv_top2_gate_up_bf16; a dropped row stays
-    unwritten in the int8 kernel and in the top-2 kernel (the bf16 indexed kernel writes it: only its guard bands are checked)."""
+    unwritten in all three."""
     g = C.gen(900)
     for i, (M, N, K) in enumerate(C.SWIGLU_SHARED):
         o = C.operands(C.Case(False, False, M, N, K, 600 + i))
@@ -252,7 +252,7 @@ def test_swiglu_forms_at_ragged_rows_and_drops(dev):
             for c in range(2):
                 sl, ex = slot[c * T:(c + 1) * T], o.expert[c * T:(c + 1) * T]
                 q = _gemv(dev, o, True, act=C.ACT_SWIGLU_PAIR, idx=ex, keep=sl, unwritten=_dropped(sl))
-                b = _gemv(dev, o, False, act=C.ACT_SWIGLU_PAIR, idx=ex, keep=sl, free=_dropped(sl))
+                b = _gemv(dev, o, False, act=C.ACT_SWIGLU_PAIR, idx=ex, keep=sl, unwritten=_dropped(sl))
                 kept = [t for t in range(T) if sl[t] >= 0]
                 assert torch.equal(_bits(q[kept]), _bits(b[kept])), (T, N, K, name, c)
                 assert torch.equal(_bits(q[kept]), _bits(act[c * T:(c + 1) * T][kept])), (T, N, K, name, c)
