@@ -127,6 +127,24 @@ int mp_quantize_rows_w8_bf16(const void* W, int64_t ldw, int64_t rows, int K, vo
 int mp_gemv_w8_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, const float* scale, int64_t strideScale, void* y,
                     int64_t ldy, const float* bias, const void* residual, int64_t ldr, const int* w_index, const float* row_scale,
                     const int* row_keep, int M, int N, int K, int act, int out_dtype, float alpha, hipStream_t stream);
+/* 4-bit NF4 decode weights (the reference's load_in_4bit with bnb_4bit_quant_type="nf4": model/builder.py:41-47, chat.py:89-98).  The format
+ * (csrc/nf4.h): a weight is a 4-bit code into the sixteen-entry NF4 table of QLoRA; 64 consecutive k of a row share one fp32 absmax; byte j of
+ * a row is code[2j] << 4 | code[2j + 1].  Quantiser, per row of W [rows, K] bf16 (ldw) and per block of 64: absmax = max |w|, inv = absmax > 0 ?
+ * 1 / absmax : 0, v = w * inv, code = the number of i in 0..14 with v > T[i], T[i] = fp32(((double)NF4[i] + NF4[i + 1]) / 2) — every step one
+ * fp32 operation in that order, a tie goes to the lower code, a zero block gets absmax 0 and codes 7.  codes: uint8 [rows, K / 2] (ldc_bytes),
+ * absmax: fp32 [rows, K / 64] (lda).  The absmax is kept in fp32: bitsandbytes' second, 8-bit quantisation of it is not built.  Called once per
+ * matrix (rows = E * N for an expert tensor), not on the hot path.  K % 64 == 0, ldw >= K, ldc_bytes >= K / 2, lda >= K / 64 (MP_ERR_SHAPE). */
+int mp_quantize_blocks_nf4_bf16(const void* W, int64_t ldw, int64_t rows, int K, void* codes, int64_t ldc_bytes, float* absmax, int64_t lda,
+                                hipStream_t stream);
+/* mp_gemv_bf16 on those codes (activations stay bf16): acc[m, n] = sum over blocks b of absmax[n, b] * sum_{k in b} bf16(NF4[code[n, k]]) *
+ * x[m, k] in fp32 — the table rounded to bf16 (nearest even; the sixteen values stay distinct), a fixed summation order — then mp_gemv_bf16's
+ * epilogues and rounding points (NONE, SWIGLU_PAIR, residual, fp32 output; the indexed expert form with codes + w_index[m] * strideW_bytes
+ * and absmax + w_index[m] * strideA).  A row with row_keep[m] < 0 streams no weights: its output is the residual (0 without one), and the
+ * SWIGLU_PAIR form leaves its row unwritten.  No bias and no other activation (MP_ERR_ARG).  1 <= M <= 8, K % 64 == 0, ldw_bytes % 16 == 0 and
+ * >= K / 2, strideW_bytes % 16 == 0, lda >= K / 64 (MP_ERR_SHAPE). */
+int mp_gemv_w4_bf16(const void* x, int64_t ldx, const void* codes, int64_t ldw_bytes, int64_t strideW_bytes, const float* absmax, int64_t lda,
+                    int64_t strideA, void* y, int64_t ldy, const float* bias, const void* residual, int64_t ldr, const int* w_index,
+                    const float* row_scale, const int* row_keep, int M, int N, int K, int act, int out_dtype, float alpha, hipStream_t stream);
 /* Top-2 MoE decode rows (tokens <= 8), the expert GEMVs over the 2 * tokens entries of mp_moe_route_top2's layout (entry c * tokens + t =
  * choice c of token t; expert[e], slot[e] < 0 = dropped, weight[e]).  gate|up: act[e, :N/2] = SwiGLU-paired x[t] . W[expert[e]] (W [E, N, K]
  * interleaved gate|up rows; dropped entries are skipped and their rows left unwritten).  down: y[t] = residual[t] + sum over the kept choices

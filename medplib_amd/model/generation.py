@@ -340,11 +340,12 @@ class GenerationMixin:
         """The prologue and epilogue of a decode entry point: adapters under expert parallelism are refused before any state changes, the
         calling stream is ordered behind the side streams, the model is in eval mode and, with adapters attached, decodes on their shadow
         merge (adapters_merged()); leaving the block — also on an exception or when a generator is closed early — puts the plain weights
-        and the mode back.  In 8-bit mode (enable_decode_8bit) the copies are re-quantised here, before anything is captured, when the parameters were
+        and the mode back.  In 8-bit or 4-bit mode (enable_decode_8bit / enable_decode_4bit) the copies are re-quantised here, before anything is captured, when the parameters were
         written since they were made.  Yields the ExitStack that holds the merge: close() it to have the plain weights back before the block ends."""
         self._require_shadowable(who)
         self.sync_side_streams()
         self._refresh_decode_8bit(who)
+        self._refresh_decode_4bit(who)
         was_training = self.training
         self.train(False)
         try:
@@ -368,7 +369,8 @@ class GenerationMixin:
         training and export keep the bf16 weights and their bits; lm_head, the embeddings, the norms and the MoE gate stay as they are; the
         activations stay bf16 (W8A16: no int8 activations, no outlier split).  NotImplementedError, with the mode left as it was, for top-2
         routing, the residual MoE, expert parallelism, attached adapters (merge_and_unload() first) and dimensions that are no multiple of 16.
-        enable_decode_8bit(False) drops the copies: today's path, bit for bit."""
+        enable_decode_8bit(False) drops the copies: today's path, bit for bit.  Exclusive with enable_decode_4bit: enabling one mode drops the
+        other's copies."""
         llm = self.model.llm
         if not on:
             llm.drop_decode_weights_w8()
@@ -389,6 +391,42 @@ class GenerationMixin:
             raise NotImplementedError(f"{who}() in 8-bit decode mode: {why} (or enable_decode_8bit(False))")
         if llm.w8_epoch != ops.PARAM_EPOCH:
             llm.quantize_decode_weights()
+
+    # ------------------------------------------------------------------ 4-bit NF4 decode weights (the reference's load_in_4bit, nf4)
+    @property
+    def decode_4bit(self):
+        """Whether the decode steps stream the NF4 copies of the decoder projections."""
+        return self.model.llm.w4 is not None
+
+    def enable_decode_4bit(self, on=True):
+        """The reference's load_in_4bit with bnb_4bit_quant_type="nf4" (model/builder.py:41-47, chat.py:89-98; bitsandbytes) as a SPEED mode of
+        the decode steps, like enable_decode_8bit and exclusive with it (enabling one drops the other's copies): NF4 copies of the decoder's
+        qkv, o, gate|up and down projections — 4-bit codes into QLoRA's table with one fp32 absmax per 64 weights, 0.5625 bytes per weight
+        (LlamaStack.quantize_decode_weights_nf4) — are added beside the bf16 weights, and every single-token decode step of evaluate / generate
+        / generate_sample / generate_beam / generate_stream, captured or looped, streams them.  The absmax stays fp32 (no double
+        quantisation), the table is NF4 only (no fp4), and the GEMV multiplies with the table rounded to bf16.  Prefill, training and export
+        keep the bf16 weights and their bits; lm_head, the embeddings, the norms and the MoE gate stay as they are.  NotImplementedError, with
+        the mode left as it was, for top-2 routing, the residual MoE, expert parallelism, attached adapters (merge_and_unload() first) and
+        dimensions that are no multiple of 64.  enable_decode_4bit(False) drops the copies: today's path, bit for bit."""
+        llm = self.model.llm
+        if not on:
+            llm.drop_decode_weights_w4()
+            return self
+        self._refuse_in_shadow("enable_decode_4bit")
+        self.sync_side_streams()
+        llm.quantize_decode_weights_nf4()
+        return self
+
+    def _refresh_decode_4bit(self, who):
+        """_refresh_decode_8bit for the NF4 copies."""
+        llm = self.model.llm
+        if llm.w4 is None:
+            return
+        why = llm.decode_w4_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"{who}() in 4-bit decode mode: {why} (or enable_decode_4bit(False))")
+        if llm.w4_epoch != ops.PARAM_EPOCH:
+            llm.quantize_decode_weights_nf4()
 
     def _graph_decode_ok(self):
         """Whether the captured step computes what the token-by-token loop computes for this model: top-1, or top-2 on one rank without the

@@ -78,6 +78,8 @@ class LlamaStack:
         self.fuse_decode_routing = True       # decode rows: post-attention norm + gate + routing in one launch
         self.w8 = None                     # 8-bit decode mode: per layer {"qkv" | "o" | "gu" | "down": (codes, scale)}, or None (off): quantize_decode_weights / drop_decode_weights_w8
         self.w8_epoch = None               # ops.PARAM_EPOCH the copies were quantised at
+        self.w4 = None                     # 4-bit decode mode: per layer {"qkv" | "o" | "gu" | "down": (codes, absmax)}, or None (off): quantize_decode_weights_nf4 / drop_decode_weights_w4; never set together with w8
+        self.w4_epoch = None               # ops.PARAM_EPOCH the NF4 copies were quantised at
         # RoPE in the qkv GEMM's epilogue (mp_gemm_qkv_rope_bf16) wants the q / k head rows interleaved in blocks of 32; the plain
         # fused qkv weight stays (decode GEMVs, the LoRA path's dgrad transposes, export), the interleaved copy (+3.2 GB of 288 at
         # 7B) serves every multi-row forward.  Rebuilt whenever the qkv weights change (refresh_fused_qkv).
@@ -106,20 +108,28 @@ class LlamaStack:
 
     W8_KEYS = ("qkv", "o", "gu", "down")
 
-    def decode_w8_unsupported(self):
-        """Why this stack cannot decode from 8-bit copies (a sentence), or None."""
+    def _decode_copies_unsupported(self, bits, multiple, why_multiple):
+        """Why this stack cannot decode from `bits`-bit copies (a sentence), or None: one list for both modes."""
         cfg = self.cfg
         if any(i in self.moe_layers for i in range(len(self.layers))) and cfg.top_k_experts != 1:
-            return "top-2 expert routing has no 8-bit expert GEMVs (top_k_experts == 1 only)"
+            return f"top-2 expert routing has no {bits}-bit expert GEMVs (top_k_experts == 1 only)"
         if cfg.use_residual:
             return "the residual MoE (use_residual) decodes through the GEMM path, which reads the bf16 weights"
         if self.ep is not None:
-            return "expert parallelism keeps the experts sharded; the 8-bit expert GEMVs run on one rank"
+            return f"expert parallelism keeps the experts sharded; the {bits}-bit expert GEMVs run on one rank"
         if self.lora is not None:
-            return "attached adapters rewrite the bf16 weights under the 8-bit copies (adapters_merged()): call merge_and_unload() first"
-        if cfg.hidden_size % 16 or cfg.intermediate_size % 16:
-            return f"hidden_size={cfg.hidden_size} and intermediate_size={cfg.intermediate_size} must be multiples of 16 (16 codes per 16-byte load)"
+            return f"attached adapters rewrite the bf16 weights under the {bits}-bit copies (adapters_merged()): call merge_and_unload() first"
+        if cfg.hidden_size % multiple or cfg.intermediate_size % multiple:
+            return f"hidden_size={cfg.hidden_size} and intermediate_size={cfg.intermediate_size} must be multiples of {multiple} ({why_multiple})"
         return None
+
+    def decode_w8_unsupported(self):
+        """Why this stack cannot decode from 8-bit copies (a sentence), or None."""
+        return self._decode_copies_unsupported(8, 16, "16 codes per 16-byte load")
+
+    def decode_w4_unsupported(self):
+        """Why this stack cannot decode from NF4 copies (a sentence), or None."""
+        return self._decode_copies_unsupported(4, 64, "one absmax per block of 64 weights")
 
     def quantize_decode_weights(self):
         """8-bit decode mode on: row-wise absmax int8 copies (ops.quantize_rows_w8, bitsandbytes' weight format) of every layer's qkv, o, gate|up
@@ -130,6 +140,7 @@ class LlamaStack:
         why = self.decode_w8_unsupported()
         if why is not None:
             raise NotImplementedError(f"8-bit decode weights: {why}")
+        self.drop_decode_weights_w4()      # the two modes are exclusive
         self.w8 = [{k: ops.quantize_rows_w8(lw[k]) for k in self.W8_KEYS} for lw in self.layers]
         self.w8_epoch = ops.PARAM_EPOCH
 
@@ -137,11 +148,33 @@ class LlamaStack:
         """8-bit decode mode off: the copies are dropped and every decode row reads the bf16 weights again."""
         self.w8 = self.w8_epoch = None
 
+    def quantize_decode_weights_nf4(self):
+        """4-bit decode mode on: NF4 copies (ops.quantize_blocks_nf4: 4-bit codes, one fp32 absmax per 64 weights) of the projections the 8-bit
+        mode copies, beside the bf16 weights (+ 0.28 of the decoder's bf16 bytes); the 8-bit copies, if any, are dropped.  While self.w4 is set,
+        every decode row streams them.  Stamped with ops.PARAM_EPOCH.  NotImplementedError (and nothing changed) where the mode is not built."""
+        why = self.decode_w4_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"4-bit decode weights: {why}")
+        self.drop_decode_weights_w8()      # the two modes are exclusive
+        self.w4 = [{k: ops.quantize_blocks_nf4(lw[k]) for k in self.W8_KEYS} for lw in self.layers]
+        self.w4_epoch = ops.PARAM_EPOCH
+
+    def drop_decode_weights_w4(self):
+        """4-bit decode mode off: the copies are dropped and every decode row reads the bf16 weights again."""
+        self.w4 = self.w4_epoch = None
+
+    def _decode_copies(self, i):
+        """Layer i's quantised copies of whichever mode is on (8-bit or NF4), or None: what a decode row hands down to _row_proj as q8."""
+        if self.w8 is not None:
+            return self.w8[i]
+        return self.w4[i] if self.w4 is not None else None
+
     def _row_proj(self, lw, key, a, q8, **kw):
-        """THE selector of a decode-row projection (at most 8 rows): the 8-bit GEMV on the layer's copies q8 (self.w8[i], handed down only
-        for a decode row) or the bf16 GEMV on lw[key]."""
+        """THE selector of a decode-row projection (at most 8 rows): the GEMV of the mode that is on — NF4 while self.w4 is set, else 8-bit —
+        on the layer's quantised copies q8 (_decode_copies(i), handed down only for a decode row), or the bf16 GEMV on lw[key]."""
         if q8 is not None:
-            return ops.gemv_w8(a, *q8[key], **kw)
+            quant_gemv = ops.gemv_w4 if self.w4 is not None else ops.gemv_w8
+            return quant_gemv(a, *q8[key], **kw)
         return ops.gemv(a, lw[key], **kw)
 
     def enable_expert_parallel(self, ep):
@@ -254,7 +287,7 @@ class LlamaStack:
     def _expert_gemvs_top1(self, lw, h, x, expert, slot, weight, q8=None):
         """Decode rows, top-1: each row streams its own expert's matrices (GEMV with a device-side expert index); the combine weight, the
         capacity drop and the residual ride in the down projection's epilogue.  Behind _mlp's routing and behind decode_step's fused one."""
-        if q8 is not None:         # (the 8-bit gate|up also skips a dropped row's weights; its act row stays unwritten and the down projection never reads it)
+        if q8 is not None:         # (the 8-bit and NF4 gate|up also skip a dropped row's weights; its act row stays unwritten and the down projection never reads it)
             act = self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR, w_index=expert, row_keep=slot)
         else:                      # (the bf16 kernel would skip it too, given row_keep; the recorded launch traces pin this call without it)
             act = self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR, w_index=expert)
@@ -269,7 +302,7 @@ class LlamaStack:
     def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None, pass_dev=None, q8=None):
         """x + MLP(h): h = post-attention RMSNorm output [T,d], x = residual stream [T,d]; gate = (logits, gates) when the caller's fused
         norm kernel already produced them (ops.rmsnorm_gate); needed = (rows, mask) when only those output rows are read (the last layer);
-        rstd: the folded post-attention norm (h is None then); q8: the layer's 8-bit copies when the rows are decode rows.  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
+        rstd: the folded post-attention norm (h is None then); q8: the layer's 8-bit or NF4 copies when the rows are decode rows.  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
         cfg, T = self.cfg, x.shape[0]
         if i not in self.moe_layers:
             if T <= 8:
@@ -446,11 +479,11 @@ class LlamaStack:
             and d in ops.RMSNORM_GATE_DIMS and ops.gemm_fold_ok(B * S, 3 * d, d) and ops.gemm_fold_ok(self.capacity(B * S), 2 * cfg.intermediate_size, d)
         self.folded_layers = 0
         last = len(self.layers) - 1
-        # 8-bit decode mode: only a decode row (a cached step behind the prefill) streams the copies, never a short prefill or a cache-free pass
-        w8_row = self.w8 is not None and kv_cache is not None and pos0 > 0 and B * S <= 8
+        # 8-bit / 4-bit decode mode: only a decode row (a cached step behind the prefill) streams the copies, never a short prefill or a cache-free pass
+        w8_row = (self.w8 is not None or self.w4 is not None) and kv_cache is not None and pos0 > 0 and B * S <= 8
         for i, lw in enumerate(self.layers):
             folded = fold and "qkv_rope_f" in lw
-            q8 = self.w8[i] if w8_row else None
+            q8 = self._decode_copies(i) if w8_row else None
             q5 = self._qkv(lw, x, S, pos0, folded, q8).unflatten(0, (B, S)).unflatten(2, (3, H, D))
             if kv_cache is not None:
                 kv_cache["k"][i][:, pos0:pos0 + S].copy_(q5[:, :, 1])
@@ -497,11 +530,11 @@ class LlamaStack:
         H, D, E, k = cfg.num_attention_heads, cfg.head_dim, cfg.num_experts, cfg.top_k_experts
         x = emb.reshape(B, d)
         self.gate_pass += 1
-        # input_layernorm inside the qkv GEMV (same bits, one launch less per layer); the norm-folded launches have no 8-bit twins: 8-bit mode
-        # takes the unfused branches
-        fold = self.w8 is None and ops.gemv_rmsnorm_ok(B, d, head_dim=D, swiglu_n=2 * cfg.intermediate_size)
+        # input_layernorm inside the qkv GEMV (same bits, one launch less per layer); the norm-folded launches have no 8-bit or NF4 twins: those modes
+        # take the unfused branches
+        fold = self.w8 is None and self.w4 is None and ops.gemv_rmsnorm_ok(B, d, head_dim=D, swiglu_n=2 * cfg.intermediate_size)
         for i, lw in enumerate(self.layers):
-            q8 = self.w8[i] if self.w8 is not None else None
+            q8 = self._decode_copies(i)
             if fold:                                            # norm + projection + RoPE + cache append: one launch, the three launches' bits
                 qkv = ops.gemv_rmsnorm_rope_append(x, lw["ln1"], cfg.rms_norm_eps, lw["qkv"], self.cos, self.sin, kv_cache["k"][i],
                                                    kv_cache["v"][i], counters[0:1], H, D, err=kv_cache["err"])

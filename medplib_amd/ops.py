@@ -357,6 +357,39 @@ def gemv_w8(x, codes, scale, bias=None, residual=None, act=ACT_NONE, out_dtype=t
     return out
 
 
+def quantize_blocks_nf4(w):
+    """NF4 copy of a projection (QLoRA's 4-bit table with one fp32 absmax per 64 weights of a row; csrc/nf4.h): w [N, K] or [E, N, K] bf16,
+    K % 64 == 0 -> (codes uint8 [..., K/2] with byte j = code[2j] << 4 | code[2j + 1], absmax fp32 [..., K/64]); a zero block gets absmax 0
+    and codes 7."""
+    _chk(w, torch.bfloat16, "quantize_blocks_nf4.w")
+    assert w.is_contiguous() and w.dim() in (2, 3)
+    K = w.shape[-1]
+    if K % 64:
+        raise ValueError(f"quantize_blocks_nf4.w: K = {K} must be a multiple of 64 (one absmax per 64 weights)")
+    codes = torch.empty(w.shape[:-1] + (K // 2,), dtype=torch.uint8, device=w.device)
+    absmax = torch.empty(w.shape[:-1] + (K // 64,), dtype=torch.float32, device=w.device)
+    lib().call("mp_quantize_blocks_nf4_bf16", _p(w), K, w.numel() // K, K, _p(codes), K // 2, _p(absmax), K // 64, _stream())
+    return codes, absmax
+
+
+def gemv_w4(x, codes, absmax, bias=None, residual=None, act=ACT_NONE, out_dtype=torch.bfloat16, alpha=1.0, w_index=None, row_scale=None,
+            row_keep=None):
+    """gemv() on the NF4 copy of w (quantize_blocks_nf4): sum over blocks of absmax[n, b] * (x . bf16(NF4[codes[n, b]])) in fp32, then gemv's
+    epilogues.  x [M <= 8, K] bf16; codes [N, K/2] uint8 with absmax [N, K/64], or with w_index [E, N, K/2] and [E, N, K/64].  Only ACT_NONE /
+    ACT_SWIGLU_PAIR and no bias (the library refuses the rest); a row with row_keep[m] < 0 streams no weights."""
+    _chk(x, torch.bfloat16, "gemv_w4.x"); _chk(codes, torch.uint8, "gemv_w4.codes"); _chk(absmax, torch.float32, "gemv_w4.absmax")
+    M, K = x.shape
+    N = codes.shape[-2]
+    assert x.stride(1) == 1 and codes.stride(-1) == 1 and codes.shape[-1] * 2 == K
+    assert absmax.stride(-1) == 1 and absmax.shape[:-1] == codes.shape[:-1] and absmax.shape[-1] * 64 == K
+    out = torch.empty((M, N // 2 if act == ACT_SWIGLU_PAIR else N), dtype=out_dtype, device=x.device)
+    lib().call("mp_gemv_w4_bf16", _p(x), x.stride(0), _p(codes), codes.stride(-2), codes.stride(0) if codes.dim() == 3 else 0, _p(absmax),
+               absmax.stride(-2), absmax.stride(0) if absmax.dim() == 3 else 0, _p(out), out.stride(0), _p(bias), _p(residual),
+               residual.stride(0) if residual is not None else 0, _p(w_index), _p(row_scale), _p(row_keep), M, N, K, act, _dt(out_dtype),
+               float(alpha), _stream())
+    return out
+
+
 def gemm_batched(a, w, out, m_dev=None, bias=None, act=ACT_NONE):
     """a [E,M,K], w [E,N,K], out [E,M,N] (bf16 or f32); m_dev int32 [E] device row counts."""
     _chk(a, torch.bfloat16, "gemm_batched.a"); _chk(w, torch.bfloat16, "gemm_batched.w")

@@ -74,13 +74,14 @@ def parse_args(argv):
 def check_placement(args):
     """This build computes in bf16 on the GPU: every other --precision / --device_map (the reference's default is 'cpu') and the 4-bit /
     fp16 loads are refused, like --cpu_only in the eval walk.  --load-8bit passes: the decode steps then stream 8-bit weight copies
-    (ModelWorker.__init__)."""
+    (ModelWorker.__init__).  --load-4bit stays refused by the worker; the model has the mode (MedPLIBForCausalLM.enable_decode_4bit())."""
     if args.device_map != "cuda":
         raise NotImplementedError(f"--device_map {args.device_map}: this build has no CPU path (the HIP library is the only implementation); "
                                   "pass --device_map cuda")
     if args.precision != "bf16" or args.load_4bit or args.load_fp16:
         raise ValueError("this build computes in bf16 (the worker's own precision): --precision bf16, no --load-4bit / --load-fp16 "
-                         "(--load-8bit: 8-bit weight copies for the decode steps, activations in bf16)")
+                         "(--load-8bit: 8-bit weight copies for the decode steps, activations in bf16; NF4 copies: the model's "
+                         "enable_decode_4bit(), not a worker flag)")
 
 
 def open_model(args, tokenizer=None):

@@ -22,9 +22,12 @@ ap.add_argument("--kinds", default="dense,top1")
 ap.add_argument("--beams", default="1,2,4,8")
 ap.add_argument("--out", default="")
 ap.add_argument("--w8", action="store_true", help="8-bit decode weights on (enable_decode_8bit) for the model steps")
+ap.add_argument("--w4", action="store_true", help="4-bit NF4 decode weights on (enable_decode_4bit) for the model steps")
 args = ap.parse_args()
+assert not (args.w8 and args.w4), "--w8 and --w4 are exclusive"
 dev = torch.device("cuda:0")
-res = {"protocol": f"slope between {args.new} and {4 * args.new} generated tokens, fastest of 3 calls each, eos off", "steps": {}, "kernels": {}}
+res = {"protocol": f"slope between {args.new} and {4 * args.new} generated tokens, fastest of 3 calls each, eos off", "steps": {}, "kernels": {},
+       "decoder_weight_bytes_streamed_per_weight": 0.5625 if args.w4 else 1.0 if args.w8 else 2.0}     # NF4: half a byte + an fp32 absmax per 64
 
 
 def event_ms(fn, iters):
@@ -70,6 +73,8 @@ for kind in args.kinds.split(","):
     model = (LISAForCausalLM if dense else MedPLIBForCausalLM)(cfg, device=dev).eval()
     if args.w8:
         model.enable_decode_8bit(True)
+    if args.w4:
+        model.enable_decode_4bit(True)
     L, V = 64, cfg.vocab_size
     ids = torch.randint(3, 31999, (1, L), generator=g)
     ids[0, 0] = 1; ids[0, 34], ids[0, 35], ids[0, 36] = V - 2, -200, V - 1

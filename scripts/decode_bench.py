@@ -1,7 +1,8 @@
 """evaluate() at the 7B dimensions: prefill + greedy single-token decode steps with the KV cache.  Prints ms per
 decode step and the HBM rate of the weight stream (every decode step reads all LLM weights once: GEMV-bound).
-python scripts/decode_bench.py [--new 32] [--dense] [--w8]
---w8: the same slope with 8-bit decode weights on (enable_decode_8bit: int8 copies of the decoder projections, bf16 lm_head)."""
+python scripts/decode_bench.py [--new 32] [--dense] [--w8 | --w4]
+--w8: the same slope with 8-bit decode weights on (enable_decode_8bit: int8 copies of the decoder projections, bf16 lm_head).
+--w4: with 4-bit NF4 decode weights on (enable_decode_4bit: 0.5625 bytes per decoder weight, bf16 lm_head)."""
 import argparse
 import json
 import os
@@ -19,7 +20,9 @@ ap.add_argument("--new", type=int, default=32)
 ap.add_argument("--dense", action="store_true")
 ap.add_argument("--no-fuse-routing", action="store_true", help="A/B: separate rmsnorm / gate / route launches in the decode step")
 ap.add_argument("--w8", action="store_true", help="8-bit decode weights (the worker's --load-8bit): the decode steps stream int8 copies")
+ap.add_argument("--w4", action="store_true", help="4-bit NF4 decode weights (enable_decode_4bit): the decode steps stream NF4 copies")
 args = ap.parse_args()
+assert not (args.w8 and args.w4), "--w8 and --w4 are exclusive"
 dev = torch.device("cuda:0")
 cfg = MedPLIBConfig.medplib_7b(moe_enable=not args.dense)
 model = (LISAForCausalLM if args.dense else MedPLIBForCausalLM)(cfg, device=dev).eval()
@@ -27,6 +30,8 @@ if args.no_fuse_routing:
     model.model.llm.fuse_decode_routing = False
 if args.w8:
     model.enable_decode_8bit(True)
+if args.w4:
+    model.enable_decode_4bit(True)
 g = torch.Generator().manual_seed(0)
 L, V = 64, cfg.vocab_size
 ids = torch.randint(3, 31999, (1, L), generator=g)
@@ -50,6 +55,8 @@ per_layer = 4 * d * d + 3 * d * ff                       # one expert's MLP is r
 wbytes = (cfg.num_hidden_layers * per_layer + V * d) * 2
 if args.w8:                                              # what a step streams: one byte per decoder weight, an fp32 scale per output row, the bf16 lm_head
     wbytes = cfg.num_hidden_layers * (per_layer + 4 * (3 * d + d + 2 * ff + d)) + V * d * 2
+if args.w4:                                              # half a byte per decoder weight + an fp32 absmax per 64 (0.5625 B per weight), the bf16 lm_head
+    wbytes = cfg.num_hidden_layers * (per_layer // 2 + 4 * (per_layer // 64)) + V * d * 2
 print(json.dumps({"metric": "decode ms/token (evaluate(), batch 1, KV cache)", "value": round(ms, 3), "total_ms_for_%d_tokens" % args.new: round(res[args.new] * 1e3, 1),
                   "weight_bytes_per_token": wbytes, "weight_stream_GBps": round(wbytes / ms / 1e6, 1), "frac_of_8TBps": round(wbytes / (ms * 1e-3) / 8e12, 4),
-                  "moe": not args.dense, "w8": bool(args.w8), "decode_path": model.last_decode_path, "generated": int(out_ids.shape[1] - L)}))
+                  "moe": not args.dense, "w8": bool(args.w8), "w4": bool(args.w4), "decode_path": model.last_decode_path, "generated": int(out_ids.shape[1] - L)}))
