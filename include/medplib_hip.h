@@ -115,6 +115,16 @@ int mp_gemm_bf16_nt_batched_rows(const void* A, int64_t lda, int64_t strideA, co
 int mp_gemv_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy, const float* bias,
                  const void* residual, int64_t ldr, const int* w_index, const float* row_scale, const int* row_keep, int M, int N, int K,
                  int act, int out_dtype, float alpha, hipStream_t stream);
+/* mp_gemv_bf16's indexed (expert) form with one weight stream per EXPERT instead of one per row: the rows of a ragged decode batch
+ * (generate_batch) that name the same expert share every loaded W vector, in passes of at most four rows; an expert no kept row names and
+ * a dropped row (row_keep[m] < 0) stream nothing.  W [E, N, K]; w_index is required; act MP_ACT_NONE (y = residual + row_scale[m] *
+ * bf16(acc); a dropped row is the residual's own bits, +0 without one) or MP_ACT_SWIGLU_PAIR (y [M, N/2]; a dropped row is left unwritten);
+ * bf16 output.  Contract: row for row bit-identical with mp_gemv_bf16 given the same arguments (the same per-lane summation order, wave
+ * reduction and K-part order; the K-split form under the same predicate, N <= 4096 and K >= 4096).  A row whose w_index lies outside [0, E)
+ * reads no weights and is stored as a dropped row.  1 <= M <= 8, K % 8 == 0, E >= 1 (MP_ERR_SHAPE); other activations MP_ERR_ARG. */
+int mp_gemv_grouped_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy, const void* residual,
+                         int64_t ldr, const int* w_index, const float* row_scale, const int* row_keep, int M, int N, int K, int E, int act,
+                         hipStream_t stream);
 /* 8-bit decode weights (the reference worker's --load-8bit: model/serve/model_worker.py:72,100,642 -> builder.py:39, bitsandbytes' row-wise
  * absmax format).  Quantiser, per row of W [rows, K] bf16 (ldw): scale[row] = absmax / 127 (fp32), codes[row, k] = rint(float(W[row, k]) *
  * (127 / absmax)) half to even as int8 (ldc); every step one fp32 operation in that order; a zero row gets scale 0 and codes 0.  Called
@@ -197,6 +207,15 @@ int mp_attention_fwd_bf16(const void* Q, int64_t q_sb, int64_t q_ss, const void*
                           int Sq, int Sk, int D, int causal, float scale, int variant, const int* sk_dev, hipStream_t stream);
 /* (sk_dev, optional: the number of valid keys, <= Sk, read from device memory — the KV-cache length of a decode step that lives in
  * a HIP graph, where launch arguments cannot change from token to token.) */
+/* The single-query decode step of mp_attention_fwd_bf16 (Sq = 1, no mask, not causal) with a key count per SEQUENCE: sequence b attends to
+ * its first min(Sk, sk_dev[b]) keys (sk_dev int32 [B], device) — the ragged rows of generate_batch.  Q, O [B, H*D] (batch strides q_sb,
+ * o_sb), K, V [B, Sk, H, D].  Row b has the bits of mp_attention_fwd_bf16 on the same tensors with the shared count sk_dev[b]: the same
+ * kernel, the same number of key splits, a sequence whose count leaves whole splits empty included.  Without the registered split workspace
+ * a cache that needs more than one split takes the tiled kernel, one launch per sequence; a cache that does not fit the workspace is
+ * MP_ERR_WORKSPACE as there.  D 64 or 128, strides multiples of 8, Sk <= 31744 (MP_ERR_SHAPE); null operands MP_ERR_ARG. */
+int mp_attention_decode_rows_bf16(const void* Q, int64_t q_sb, const void* K, int64_t k_sb, int64_t k_ss, const void* V, int64_t v_sb,
+                                  int64_t v_ss, void* O, int64_t o_sb, const int* sk_dev, int B, int H, int Sk, int D, float scale,
+                                  hipStream_t stream);
 
 /* LlamaRMSNorm (HF 4.31; medplib_moe_llama.py:121,138,286). */
 int mp_rmsnorm_bf16(const void* x, int64_t ldx, const float* w, void* y, int64_t ldy, int64_t rows, int dim, float eps,
@@ -223,6 +242,13 @@ int mp_decode_rope_append_bf16(void* qkv, int64_t ld, const float* cos_t, const 
 int mp_decode_rope_append_bounded_bf16(void* qkv, int64_t ld, const float* cos_t, const float* sin_t, void* cache_k, void* cache_v,
                                        const int* pos_dev, int B, int heads, int head_dim, int64_t cache_batch_stride,
                                        int64_t cache_seq_stride, int table_rows, int cache_rows, int* err, hipStream_t stream);
+/* mp_decode_rope_append_bounded_bf16 with a position per SEQUENCE: pos_dev is int32 [B] (device), sequence b is rotated at pos_dev[b] and its
+ * k / v are written to cache[b, pos_dev[b]] — the ragged rows of generate_batch.  The bounds rule holds per sequence: one whose position has
+ * no table or cache row writes nothing (its q included) and ORs MP_POS_ERR_* into *err; the other sequences are unaffected.  In range: the
+ * bits of mp_decode_rope_append_bounded_bf16 called on that sequence alone.  Same argument checks. */
+int mp_decode_rope_append_rows_bounded_bf16(void* qkv, int64_t ld, const float* cos_t, const float* sin_t, void* cache_k, void* cache_v,
+                                            const int* pos_dev, int B, int heads, int head_dim, int64_t cache_batch_stride,
+                                            int64_t cache_seq_stride, int table_rows, int cache_rows, int* err, hipStream_t stream);
 int mp_advance_ints(int* p, int n, int delta, hipStream_t stream);
 /* greedy next-token pick over fp32 logits (HF generate do_sample=False, MedPLIB.py:592-606). */
 int mp_argmax_rows_f32(const float* x, int64_t ld, int64_t rows, int cols, int64_t* out, hipStream_t stream);

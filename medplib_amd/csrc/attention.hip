@@ -38,6 +38,7 @@ struct AttnArgs {
   const int* sk_dev;         // optional: number of valid keys read from device memory (<= Sk); decode steps inside a HIP graph
   float* lse2;               // optional [B*H, Sq]: row log-sum-exp of the scaled scores in the log2 domain (for the backward; v2 kernel)
   int bh_chunk;              // v2 kernel: (batch, head) pairs per chunk of the workgroup order (0 = all: the plain order)
+  int sk_stride;             // decode kernel: sequence b reads sk_dev[b * sk_stride] (0 = one shared count; 1 = mp_attention_decode_rows_bf16)
 };
 
 template <int D>
@@ -698,10 +699,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a, float* __r
   __shared__ float red[16];
   __shared__ float part[KPB][D];
   __shared__ int s_ticket;
-  const int Sk = a.sk_dev ? min(a.Sk, a.sk_dev[0]) : a.Sk;
   const int tid = threadIdx.x;
   const int c = tid % CH, kg = tid / CH;
   const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
+  const int Sk = a.sk_dev ? min(a.Sk, a.sk_dev[b * a.sk_stride]) : a.Sk;      // (a count <= 0 leaves every split empty: the row's output is 0)
   const int split = blockIdx.y;
   int chunk = (Sk + NS - 1) / NS;
   chunk = ((chunk + KPB - 1) / KPB) * KPB;
@@ -869,7 +870,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a, float* __r
 }
 
 template <int D>
-int launch_attn_decode(const AttnArgs& a, hipStream_t stream) {
+int launch_attn_decode(const AttnArgs& a, hipStream_t stream, const char* name = "mp_attention_fwd_bf16(decode)") {
   float* ws = nullptr; int* tickets = nullptr; int64_t bytes = 0;
   mp_gemm_split_workspace(stream, &ws, &tickets, &bytes);
   int NS = 1;
@@ -880,9 +881,9 @@ int launch_attn_decode(const AttnArgs& a, hipStream_t stream) {
   }
   while ((a.Sk + NS - 1) / NS + 64 > DEC_MAX_CHUNK) ++NS;               // a split's scores must fit the LDS array
   if (NS > 1 && !ws) return -1;
-  if ((int64_t)a.B * a.H * NS * (D + 2) * 4 > bytes) { mp_set_error("mp_attention_fwd_bf16(decode): %d keys in %d splits do not fit the split workspace", a.Sk, NS); return MP_ERR_WORKSPACE; }
+  if ((int64_t)a.B * a.H * NS * (D + 2) * 4 > bytes) { mp_set_error("%s: %d keys in %d splits do not fit the split workspace", name, a.Sk, NS); return MP_ERR_WORKSPACE; }
   hipLaunchKernelGGL((attn_decode_kernel<D>), dim3(a.B * a.H, NS), dim3(256), 0, stream, a, ws, tickets, NS);
-  return mp_check_launch("mp_attention_fwd_bf16(decode)");
+  return mp_check_launch(name);
 }
 
 }  // namespace
@@ -927,6 +928,35 @@ extern "C" int mp_attention_fwd_bf16(const void* Q, int64_t q_sb, int64_t q_ss, 
   if (variant == 0) variant = 2;
   if (D == 64) return variant == 1 ? launch_attn<64, true>(a, stream) : launch_attn<64, false>(a, stream);
   return variant == 1 ? launch_attn<128, true>(a, stream) : launch_attn<128, false>(a, stream);
+}
+
+// The single-query decode step of RAGGED batch rows: sequence b attends to its first min(Sk, sk_dev[b]) keys.  The flash-decoding kernel with
+// a key count per sequence (AttnArgs::sk_stride = 1): the NS choice, the workspace rule and its error are launch_attn_decode's; a sequence
+// whose count leaves whole splits empty merges them with weight 0.  Without the split workspace a cache that needs NS > 1 takes the tiled
+// kernel, one launch per sequence with that sequence's count (the kernel reads one shared count per launch).
+extern "C" int mp_attention_decode_rows_bf16(const void* Q, int64_t q_sb, const void* K, int64_t k_sb, int64_t k_ss, const void* V,
+                                             int64_t v_sb, int64_t v_ss, void* O, int64_t o_sb, const int* sk_dev, int B, int H, int Sk,
+                                             int D, float scale, hipStream_t stream) {
+  MP_REQUIRE(D == 64 || D == 128, MP_ERR_SHAPE, "mp_attention_decode_rows_bf16: head_dim %d unsupported (64/128)", D);
+  MP_REQUIRE(B > 0 && H > 0 && Sk > 0, MP_ERR_SHAPE, "mp_attention_decode_rows_bf16: bad shape");
+  MP_REQUIRE((k_ss % 8 == 0) && (v_ss % 8 == 0) && (q_sb % 8 == 0) && (k_sb % 8 == 0) && (v_sb % 8 == 0) && (o_sb % 8 == 0), MP_ERR_SHAPE,
+             "mp_attention_decode_rows_bf16: strides must be multiples of 8 elements");
+  MP_REQUIRE(Q && K && V && O && sk_dev, MP_ERR_ARG, "mp_attention_decode_rows_bf16: null operand");
+  MP_REQUIRE(Sk <= 16 * (DEC_MAX_CHUNK - 64), MP_ERR_SHAPE, "mp_attention_decode_rows_bf16: %d keys are more than the decode kernel splits", Sk);
+  AttnArgs a{(const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V, (bf16_t*)O, q_sb, q_sb, k_sb, k_ss, v_sb, v_ss, o_sb, o_sb,
+             nullptr, nullptr, nullptr, 0, 0, B, H, 1, Sk, 0, scale, sk_dev};
+  a.sk_stride = 1;
+  const char* name = "mp_attention_decode_rows_bf16";
+  const int rc = D == 64 ? launch_attn_decode<64>(a, stream, name) : launch_attn_decode<128>(a, stream, name);
+  if (rc >= 0) return rc;
+  for (int b = 0; b < B; ++b) {
+    AttnArgs r = a;
+    r.Q = a.Q + b * q_sb; r.K = a.K + b * k_sb; r.V = a.V + b * v_sb; r.O = a.O + b * o_sb;
+    r.B = 1; r.sk_dev = sk_dev + b; r.sk_stride = 0;
+    const int rt = D == 64 ? launch_attn2<64>(r, stream) : launch_attn2<128>(r, stream);
+    if (rt != MP_OK) return rt;
+  }
+  return MP_OK;
 }
 
 // Forward that also returns the row log-sum-exp (log2 domain) the backward needs; transposed-formulation kernel only (no rel-pos).

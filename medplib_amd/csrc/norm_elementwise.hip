@@ -173,17 +173,20 @@ __global__ void rope_qk_bf16_kernel(bf16_t* __restrict__ qkv, const float* __res
 // KV cache at that position.  One thread per (sequence, head, 8 rotary pairs).
 // Bounded form (err != nullptr): a position outside [0, table_rows) or [0, cache_rows) reads no table row, writes nothing (q included)
 // and thread 0 ORs MP_POS_ERR_* into *err; the unbounded entry point passes MP_POS_UNBOUNDED and no word (its bits are unchanged).
+// pos_stride: 0 = every sequence at pos_dev[0] (thread 0 alone reports, as before); 1 = sequence b at pos_dev[b] (ragged batch rows:
+// mp_decode_rope_append_rows_bounded_bf16), where the bounds rule holds per sequence — the first thread of EVERY out-of-range sequence ORs
+// that sequence's bits, the other sequences are written as usual.
 __global__ void decode_rope_append_kernel(bf16_t* __restrict__ qkv, int64_t ld, const float* __restrict__ cos_t,
                                           const float* __restrict__ sin_t, bf16_t* __restrict__ ck, bf16_t* __restrict__ cv,
-                                          const int* __restrict__ pos_dev, int B, int H, int D, int64_t c_sb, int64_t c_ss,
-                                          int table_rows, int cache_rows, int* __restrict__ err) {
+                                          const int* __restrict__ pos_dev, int pos_stride, int B, int H, int D, int64_t c_sb,
+                                          int64_t c_ss, int table_rows, int cache_rows, int* __restrict__ err) {
   const int half = D / 2, per_head = half / 8;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * H * per_head) return;
   const int c = (idx % per_head) * 8, h = (idx / per_head) % H, b = idx / (per_head * H);
-  const int pos = pos_dev[0];
+  const int pos = pos_dev[b * pos_stride];
   if (pos < 0 || pos >= table_rows || pos >= cache_rows) {
-    if (idx == 0 && err) atomicOr(err, (pos < 0 || pos >= table_rows ? MP_POS_ERR_TABLE : 0) | (pos < 0 || pos >= cache_rows ? MP_POS_ERR_CACHE : 0));
+    if (idx == b * H * per_head && (pos_stride != 0 || b == 0) && err) atomicOr(err, (pos < 0 || pos >= table_rows ? MP_POS_ERR_TABLE : 0) | (pos < 0 || pos >= cache_rows ? MP_POS_ERR_CACHE : 0));
     return;
   }
   const float* cs = cos_t + (int64_t)pos * half + c;
@@ -408,12 +411,13 @@ extern "C" int mp_rope_qk_bounded_bf16(void* qkv, int64_t ld, const float* cos_t
 
 static int decode_rope_append_launch(const char* name, void* qkv, int64_t ld, const float* cos_t, const float* sin_t, void* cache_k,
                                      void* cache_v, const int* pos_dev, int B, int heads, int head_dim, int64_t cache_batch_stride,
-                                     int64_t cache_seq_stride, int table_rows, int cache_rows, int* err, hipStream_t stream) {
+                                     int64_t cache_seq_stride, int table_rows, int cache_rows, int* err, hipStream_t stream,
+                                     int pos_stride = 0) {
   const int n = B * heads * (head_dim / 16);
   if (n == 0) return MP_OK;
   hipLaunchKernelGGL(decode_rope_append_kernel, dim3((unsigned)mp_cdiv(n, 256)), dim3(256), 0, stream, (bf16_t*)qkv, ld, cos_t, sin_t,
-                     (bf16_t*)cache_k, (bf16_t*)cache_v, pos_dev, B, heads, head_dim, cache_batch_stride, cache_seq_stride, table_rows,
-                     cache_rows, err);
+                     (bf16_t*)cache_k, (bf16_t*)cache_v, pos_dev, pos_stride, B, heads, head_dim, cache_batch_stride, cache_seq_stride,
+                     table_rows, cache_rows, err);
   return mp_check_launch(name);
 }
 
@@ -435,6 +439,18 @@ extern "C" int mp_decode_rope_append_bounded_bf16(void* qkv, int64_t ld, const f
   MP_REQUIRE(qkv && cos_t && sin_t && cache_k && cache_v && pos_dev && err, MP_ERR_ARG, "mp_decode_rope_append_bounded_bf16: null operand");
   return decode_rope_append_launch("mp_decode_rope_append_bounded_bf16", qkv, ld, cos_t, sin_t, cache_k, cache_v, pos_dev, B, heads,
                                    head_dim, cache_batch_stride, cache_seq_stride, table_rows, cache_rows, err, stream);
+}
+
+extern "C" int mp_decode_rope_append_rows_bounded_bf16(void* qkv, int64_t ld, const float* cos_t, const float* sin_t, void* cache_k,
+                                                       void* cache_v, const int* pos_dev, int B, int heads, int head_dim,
+                                                       int64_t cache_batch_stride, int64_t cache_seq_stride, int table_rows,
+                                                       int cache_rows, int* err, hipStream_t stream) {
+  MP_REQUIRE(head_dim % 16 == 0 && ld % 8 == 0 && B >= 0 && heads >= 0, MP_ERR_SHAPE, "mp_decode_rope_append_rows_bounded_bf16: bad shape");
+  MP_REQUIRE(table_rows > 0 && cache_rows > 0, MP_ERR_SHAPE,
+             "mp_decode_rope_append_rows_bounded_bf16: table_rows (%d) and cache_rows (%d) must be > 0", table_rows, cache_rows);
+  MP_REQUIRE(qkv && cos_t && sin_t && cache_k && cache_v && pos_dev && err, MP_ERR_ARG, "mp_decode_rope_append_rows_bounded_bf16: null operand");
+  return decode_rope_append_launch("mp_decode_rope_append_rows_bounded_bf16", qkv, ld, cos_t, sin_t, cache_k, cache_v, pos_dev, B, heads,
+                                   head_dim, cache_batch_stride, cache_seq_stride, table_rows, cache_rows, err, stream, 1);
 }
 
 extern "C" int mp_advance_ints(int* p, int n, int delta, hipStream_t stream) {

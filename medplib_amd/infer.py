@@ -37,6 +37,8 @@ def parse_args(argv=None):
     p.add_argument("--icl_mask_mode", default="overlay", choices=["overlay", "separate"])
     p.add_argument("--icl_mask_encoder", action="store_true", default=False)
     p.add_argument("--answers_file", default="")
+    p.add_argument("--decode_batch", default=1, type=int,
+                   help="--eval_vqa: samples decoded together per generate_batch() call (1..8); 1 = one generate() call per sample")
     p.add_argument("--colon_token_id", default=COLON_ID, type=int)
     # the model flags build_model reads (train.py)
     for name, typ, dv in (("moe_enable", lambda s: s.lower() in ("1", "true"), True), ("num_experts", int, 2), ("top_k_experts", int, 1),
@@ -90,23 +92,65 @@ def validate_seg(val, model, device, max_new_tokens=64, colon_id=COLON_ID):
 
 
 @torch.no_grad()
-def run_vqa(val, model, device, max_new_tokens=64, colon_id=COLON_ID, answers_file="", tokenizer=None):
+def _generate_together(model, samples, cuts, max_new_tokens, eos=2):
+    """The single-sample batches `samples` (prompts cut at `cuts`) through ONE generate_batch() call -> per sample the ids [1, cut + n] that
+    generate() returns for it alone (its own padding removed).  eos: generate()'s default stop id, which the VQA loop decodes with."""
+    for b in samples:
+        if any(b.get(k) is not None for k in ("mask_images", "image_token_types", "image_token_lengths")):
+            raise NotImplementedError("--decode_batch > 1 with in-context mask images (mask_images / image_token_types / image_token_lengths) "
+                                      "is not built: they are per-call arguments of generate(); use --decode_batch 1")
+    width = max(cuts)
+    ids = torch.zeros((len(samples), width), dtype=torch.int64)
+    att = torch.zeros((len(samples), width), dtype=torch.bool)
+    for r, (b, cut) in enumerate(zip(samples, cuts)):
+        ids[r, :cut] = torch.as_tensor(b["input_ids"])[0, :cut].cpu()
+        att[r, :cut] = torch.as_tensor(b["attention_mask"])[0, :cut].cpu().bool()
+    clips = [b["images_clip"] for b in samples]
+    images = torch.cat(clips) if all(torch.is_tensor(c) for c in clips) else [c for cl in clips for c in (cl if isinstance(cl, (list, tuple)) else [cl])]
+    regions = [m for b in samples for m in (b.get("region_masks") or ())]
+    valid = [v for b in samples for v in (b.get("valid_region_masks_bool") or ())]
+    out = model.generate_batch(ids, images=images, attention_mask=att, max_new_tokens=max_new_tokens, eos_token_id=eos,
+                               batch_rows=len(samples), region_masks=regions or None, valid_region_masks_bool=valid or None)
+    rows = []
+    for r, cut in enumerate(cuts):
+        n_prompt = int(att[r].sum())
+        new = out[r, n_prompt:n_prompt + max_new_tokens]        # (what follows is the eos padding up to the widest row of the group)
+        stop = (new == eos).nonzero()
+        if stop.numel():                                         # the row stopped: its answer ends on its eos
+            new = new[:int(stop[0]) + 1]
+        rows.append(torch.cat([ids[r, :cut][att[r, :cut]], new])[None])
+    return rows
+
+
+@torch.no_grad()
+def run_vqa(val, model, device, max_new_tokens=64, colon_id=COLON_ID, answers_file="", tokenizer=None, decode_batch=1):
     """-> list of generated id tensors (prompt + continuation, as HF `generate` returns them).  With `answers_file`: one JSON line
     per sample {question_id, image_path, prompt, text | output_ids, gt} (vqa_infer.py:470-480); `text` needs a tokenizer with
-    `batch_decode`, otherwise the new ids are written."""
+    `batch_decode`, otherwise the new ids are written.  decode_batch > 1: that many samples are collected per generate_batch() call (their
+    prompts are the rows of one decode step); the answers file has the same records in the same order."""
     model.eval()
+    if not 1 <= int(decode_batch) <= 8:
+        raise ValueError(f"--decode_batch {decode_batch} must lie in 1..8")
     outs = []
     fh = None
     if answers_file:
         os.makedirs(os.path.dirname(os.path.abspath(answers_file)), exist_ok=True)
         fh = open(answers_file, "a")
+    ready = {}                                                   # sample number -> its output ids, decoded ahead as part of a group
     for i in range(len(val)):
         b = dict_to_device(val[i], device)
         cut = prompt_cut(b["input_ids"], colon_id)
-        out = model.generate(b["input_ids"][:, :cut], images=b["images_clip"], attention_mask=b["attention_mask"][:, :cut],
-                             max_new_tokens=max_new_tokens, mask_images=b.get("mask_images"),
-                             image_token_types=b.get("image_token_types"), image_token_lengths=b.get("image_token_lengths"),
-                             region_masks=b.get("region_masks"), valid_region_masks_bool=b.get("valid_region_masks_bool"))
+        if decode_batch > 1:
+            if i not in ready:
+                group = [b] + [dict_to_device(val[j], device) for j in range(i + 1, min(i + decode_batch, len(val)))]
+                cuts = [prompt_cut(s["input_ids"], colon_id) for s in group]
+                ready = dict(zip(range(i, i + len(group)), _generate_together(model, group, cuts, max_new_tokens)))
+            out = ready[i]
+        else:
+            out = model.generate(b["input_ids"][:, :cut], images=b["images_clip"], attention_mask=b["attention_mask"][:, :cut],
+                                 max_new_tokens=max_new_tokens, mask_images=b.get("mask_images"),
+                                 image_token_types=b.get("image_token_types"), image_token_lengths=b.get("image_token_lengths"),
+                                 region_masks=b.get("region_masks"), valid_region_masks_bool=b.get("valid_region_masks_bool"))
         outs.append(out)
         if fh is not None:
             new_ids = torch.as_tensor(out)[:, cut:]
@@ -136,7 +180,7 @@ def main(argv=None):
     out = {}
     if args.eval_vqa:
         out["vqa_output_ids"] = run_vqa(val, model, device, args.max_new_tokens, args.colon_token_id, args.answers_file,
-                                        getattr(val, "tokenizer", None))
+                                        getattr(val, "tokenizer", None), decode_batch=args.decode_batch)
     if args.eval_seg:
         out["miou"], out["mdice"], out["per_modality"] = validate_seg(val, model, device, args.max_new_tokens, args.colon_token_id)
     return out

@@ -8,7 +8,8 @@ logits from the prefill and hands the rest to one of two drivers:
 * `_loop_steps`: the token-by-token loop over `LlamaStack.forward`, a host read per token.
 
 A policy says what a step selects and what the host keeps of it: `_single_row_policy` (one sequence, the next token chosen by a pick — the greedy
-argmax or a `_SamplePick`) and `_beam_policy` (the num_beams beams of one prompt as the rows of one step).  Each is a namespace of closures:
+argmax or a `_SamplePick`), `_beam_policy` (the num_beams beams of one prompt as the rows of one step) and `_batch_policy` (several prompts of
+different lengths as the rows of one step, each with its own position and key count).  Each is a namespace of closures:
 
     first(logits)        the selection of step 0, from the prefill's logits
     step(forward, at)    one decode step: embed the selected ids, forward(emb) -> hidden, logits, selection.  `at` is the device counters of a
@@ -17,6 +18,8 @@ argmax or a `_SamplePick`) and `_beam_policy` (the num_beams beams of one prompt
     records(upto), look(bytes, upto) -> (kept steps, done, what to yield)      the captured driver's read at a look
     loop_look(i) -> (finished, what to yield)                                  the loop's read after step i
     reorder              the loop's hook before a step (beams: HF's whole-cache _reorder_cache), or None
+    counters, forward    None, or (the batch policy) counters() -> the initial device counters of the call and forward(emb, counters, pass_dev)
+                         -> hidden, the decode step both drivers then run: the loop too, advancing the counters after every step
     needs_step, debug, n_dbg, err_also"""
 import contextlib
 import dataclasses
@@ -54,6 +57,9 @@ _REFUSED = {
                  "beams": "beam search (num_beams > 1) is not built here: call generate_beam(); the shipped eval scripts use num_beams=1"},
     "generate_sample": {"beams": "beam search (num_beams > 1) is not built; the shipped eval scripts use num_beams=1"},
     "generate_beam": {"sampling": "beam sampling (do_sample / temperature > 0 with num_beams > 1) is not built"},
+    "generate_batch": {"sampling": "sampling per batch row (do_sample / temperature > 0) is not built: the rows of a batch are decoded greedily; "
+                                   "call generate_sample()",
+                       "beams": "beam search per batch row (num_beams > 1) is not built: call generate_beam()"},
 }
 
 
@@ -120,8 +126,12 @@ class _SamplePick:
 def _raise_on_error_word(llm, cache, err, steps=None, S=None, also=""):
     """The cache's error word (MP_POS_ERR_*) after decode steps: non-zero when a bounded kernel met a position without a table or cache row."""
     if err:
-        where = "a decode step" if steps is None else (f"decode steps {steps[0]}..{steps[1]} (positions {S + steps[0] - 1}.."
-                                                       f"{S + steps[1] - 1})")
+        if steps is None:
+            where = "a decode step"
+        elif isinstance(S, (list, tuple)):       # a batch group: every row has its own prompt length
+            where = f"decode steps {steps[0]}..{steps[1]} (positions " + ", ".join(f"{n + steps[0] - 1}..{n + steps[1] - 1}" for n in S) + " of the rows)"
+        else:
+            where = f"decode steps {steps[0]}..{steps[1]} (positions {S + steps[0] - 1}..{S + steps[1] - 1})"
         raise RuntimeError(f"decode: {where} ran past the RoPE table ({llm.cos.shape[0]} rows) or the KV cache ({cache['k'][0].shape[1]} rows)"
                            f"{also}: error word {err}")
 
@@ -140,14 +150,19 @@ def _captured_steps(llm, cache, S, policy, looks):
     dev = llm.device
     # [position of the fed token, keys after appending it] and, for a pick that draws, the number of the token being generated: one
     # advance per replay bumps them all
-    counters = torch.tensor([S, S + 1] + ([1] if policy.needs_step else []), dtype=torch.int32, device=dev)
+    # (a policy with rows of different lengths supplies its own: a position and a key count per row)
+    counters = policy.counters() if policy.counters is not None else \
+        torch.tensor([S, S + 1] + ([1] if policy.needs_step else []), dtype=torch.int32, device=dev)
     # the gate's random draws (moe_gate_sampling) are keyed on the forward-pass number: the token-by-token loop gives the decode step
     # of token i pass pass0 + i, so the graph reads it from a device counter it advances itself
     pass0 = llm.gate_pass
     pass_dev = torch.tensor([pass0 + 1], dtype=torch.int32, device=dev)
 
     def step():
-        policy.step(lambda emb: llm.decode_step(emb, cache, counters, pass_dev=pass_dev), counters)
+        if policy.forward is not None:
+            policy.step(lambda emb: policy.forward(emb, counters, pass_dev), counters)
+        else:
+            policy.step(lambda emb: llm.decode_step(emb, cache, counters, pass_dev=pass_dev), counters)
         ops.advance_ints(counters, 1)
         ops.advance_ints(pass_dev, 1)
 
@@ -181,7 +196,9 @@ def _captured_steps(llm, cache, S, policy, looks):
 
 def _loop_steps(llm, cache, policy, max_new_tokens):
     """Decode token by token: after every step the host reads it (policy.loop_look) and yields; until the policy has finished, the next step
-    runs through LlamaStack.forward against the KV cache."""
+    runs through LlamaStack.forward against the KV cache — or through the policy's own forward (the batch policy: the decode step of the
+    captured driver, uncaptured, at device counters this loop advances)."""
+    counters = policy.counters() if policy.forward is not None else None
     for i in range(max_new_tokens):
         finished, out = policy.loop_look(i)
         yield out
@@ -189,11 +206,15 @@ def _loop_steps(llm, cache, policy, max_new_tokens):
             return
         if policy.reorder is not None:
             policy.reorder()
-        policy.step(lambda emb: llm.forward(emb, None, kv_cache=cache)[0], i + 1)
+        if policy.forward is not None:
+            policy.step(lambda emb: policy.forward(emb, counters, None), i + 1)
+            ops.advance_ints(counters, 1)
+        else:
+            policy.step(lambda emb: llm.forward(emb, None, kv_cache=cache)[0], i + 1)
         policy.file(i + 1)
 
 
-# ---------------------------------------------------------------------- the two selection policies
+# ---------------------------------------------------------------------- the three selection policies
 def _single_row_policy(llm, hidden, cache, max_new_tokens, stop_ids, pick, debug, captured):
     """One sequence, the next token chosen by `pick`.  Yields (generated ids so far, stopped, [hidden states of the prompt, of each fed
     token]); stops at one of `stop_ids` or at max_new_tokens.  debug: a list that receives (fp32 logits row on the host, u or None, token)
@@ -250,7 +271,7 @@ def _single_row_policy(llm, hidden, cache, max_new_tokens, stop_ids, pick, debug
         return finished, (generated, stopped, hiddens)
 
     return types.SimpleNamespace(first=lambda logits: select(logits, 0), step=step, file=file, records=lambda upto: toks[:upto], look=look,
-                                 loop_look=loop_look, reorder=None, needs_step=needs_step, debug=debug,
+                                 loop_look=loop_look, reorder=None, counters=None, forward=None, needs_step=needs_step, debug=debug,
                                  n_dbg=len(debug) if debug is not None else 0, err_also="")
 
 
@@ -327,7 +348,110 @@ def _beam_policy(llm, cache, S, max_new_tokens, nb, scorer, eos_token_id, debug,
 
     err_also = ", or the beam selection ran out of candidates (NaN logits)"
     return types.SimpleNamespace(first=first, step=step, file=file, records=lambda upto: hist[scorer.steps:upto], look=look, loop_look=loop_look,
-                                 reorder=reorder, needs_step=False, debug=debug, n_dbg=len(debug) if debug is not None else 0, err_also=err_also)
+                                 reorder=reorder, counters=None, forward=None, needs_step=False, debug=debug,
+                                 n_dbg=len(debug) if debug is not None else 0, err_also=err_also)
+
+
+def _batch_policy(llm, hiddens0, cache, lengths, max_new_tokens, stop_ids, pick, debug, captured):
+    """The B prompts of a group as the rows of one step: row b sits at its own position lengths[b] + i and sees its own lengths[b] + i + 1 keys
+    (decode_step with per-row state); the pick runs over the [B, V] logits; one record of B tokens per step.  At a look the host finds each
+    row's first stop id: the call is done when every row has stopped or at max_new_tokens, and what a row computed past its stop is discarded.
+    Yields ([generated ids so far per row], [stopped per row], [[hidden states of the prompt, of each fed token] per row]).  hiddens0: the
+    prefill's hidden states per row.  debug: a list that receives (fp32 logits [B, V] on the host, the B tokens) per kept step."""
+    d, dev, B = llm.cfg.hidden_size, llm.device, len(lengths)
+    needs_step = getattr(pick, "needs_step", False)
+    st = types.SimpleNamespace(tok=None, logits=None)        # the selected tokens (int64 [B] on the device) and the logits they came from
+    generated, hiddens = [], []                               # the loop's record: [B] tokens on the host and [B, 1, d] hidden states per step
+    if captured:
+        toks = torch.empty((max_new_tokens, B), dtype=torch.int64, device=dev)
+        hid_all = torch.empty((max_new_tokens, B, d), dtype=torch.bfloat16, device=dev)
+        h_static = torch.empty((B, 1, d), dtype=torch.bfloat16, device=dev)
+
+    def counters():
+        """[position of the fed token per row | keys after appending it per row | the number of the token being generated]"""
+        return torch.tensor(list(lengths) + [n + 1 for n in lengths] + [1], dtype=torch.int32, device=dev)
+
+    def forward(emb, ctr, pass_dev):
+        return llm.decode_step(emb, cache, None, pass_dev=pass_dev, rows=(ctr[:B], ctr[B:2 * B]))
+
+    def select(logits, step_no):
+        st.logits = logits
+        tok = pick(logits, step_no)
+        if captured and st.tok is not None:
+            st.tok.copy_(tok)
+        else:
+            st.tok = tok
+
+    def step(fwd, at):
+        emb = ops.splice_rows(llm.embed_tokens, None, st.tok, d)
+        h = fwd(emb.view(B, 1, d))
+        if captured:
+            h_static.copy_(h)
+            select(llm.next_token_logits(h.view(B, d)), at[2 * B:2 * B + 1] if needs_step else None)
+        else:
+            hiddens.append(h)
+            select(llm.next_token_logits(h.view(B, d)), at)
+
+    def file(i):
+        if captured:
+            if i:
+                hid_all[i - 1].copy_(h_static.view(B, d))
+            toks[i].copy_(st.tok)
+        else:
+            generated.append(st.tok.cpu().numpy())
+        if debug is not None:
+            debug.append((st.logits.float().cpu(), (toks[i] if captured else st.tok).tolist()))
+
+    def kept_rows(ids):
+        """ids [n, B] on the host -> per row the steps kept (up to and including its first stop id) and whether it stopped."""
+        kept, stopped = [], []
+        for b in range(B):
+            hits = [i for i, t in enumerate(ids[:, b].tolist()) if t in stop_ids]
+            kept.append(hits[0] + 1 if hits else ids.shape[0])
+            stopped.append(bool(hits))
+        return kept, stopped
+
+    def out_of(ids, kept, stopped, hidden_of):
+        return ([ids[:kept[b], b].tolist() for b in range(B)], stopped,
+                [[hiddens0[b]] + [hidden_of(i, b) for i in range(kept[b] - 1)] for b in range(B)])
+
+    def look(got, upto):
+        ids = got.view(np.int64).reshape(upto, B)
+        kept, stopped = kept_rows(ids)
+        return max(kept), all(stopped), out_of(ids, kept, stopped, lambda i, b: hid_all[i, b].view(1, 1, d))
+
+    def loop_look(i):
+        ids = np.stack(generated)
+        kept, stopped = kept_rows(ids)
+        finished = all(stopped) or len(generated) == max_new_tokens
+        if finished:
+            _raise_on_error_word(llm, cache, int(cache["err"][0]))
+        return finished, out_of(ids, kept, stopped, lambda j, b: hiddens[j][b].view(1, 1, d))
+
+    return types.SimpleNamespace(first=lambda logits: select(logits, 0), step=step, file=file, records=lambda upto: toks[:upto], look=look,
+                                 loop_look=loop_look, reorder=None, counters=counters, forward=forward, needs_step=needs_step, debug=debug,
+                                 n_dbg=len(debug) if debug is not None else 0, err_also="")
+
+
+def _row_prompt(ids, images, attention_mask, kwargs, b):
+    """Row b of a batch as one prompt -> (ids [1, L_b] without the row's padding, its CLIP images, its PromptExtras)."""
+    row = ids[b:b + 1]
+    if attention_mask is not None:
+        row = row[:, _np_ids(attention_mask)[b].astype(bool)]               # drop this row's padding
+    img = images[b] if isinstance(images, (list, tuple)) else images[b:b + 1]
+    if isinstance(images, (list, tuple)):
+        img = [img]
+    rm, rv = kwargs.get("region_masks") or (), kwargs.get("valid_region_masks_bool") or ()
+    if len(rm) > 0:            # the collator's flat list holds one entry per sample WITH regions: pick this row's
+        before = sum(1 for v in rv[:b] if any(v))
+        rm, rv = (rm[before:before + 1] if any(rv[b]) else ()), rv[b:b + 1]
+    return row, img, PromptExtras(kwargs.get("mask_images"), kwargs.get("image_token_types"), kwargs.get("image_token_lengths"), rm, rv)
+
+
+def _padded_rows(rows, eos_token_id):
+    """Output rows (prompt + answer, int64 [L_b + n_b] each) -> int64 [B, max], right-padded with eos: HF generate's layout."""
+    n = max(r.shape[0] for r in rows)
+    return torch.from_numpy(np.stack([np.concatenate([r, np.full(n - r.shape[0], eos_token_id, np.int64)]) for r in rows]))
 
 
 # ---------------------------------------------------------------------- the model's generation surface
@@ -440,16 +564,36 @@ class GenerationMixin:
         """Whether a call decodes through the captured graph (more than two tokens: one replay at least), else token by token."""
         return bool(self.decode_with_graph and max_new_tokens > 2 and self._graph_decode_ok())
 
-    def _prefill(self, ids, images_clip, extras, max_new_tokens, rows=1):
-        """The spliced prompt through the stack at batch 1, into row 0 of a KV cache of `rows` rows and S + max_new_tokens positions (allocated
-        here, so the RoPE tables have grown before anything is captured); the prompt's K/V copied to the other rows.  -> (hidden, cache, S)."""
+    def _plan_embeds(self, ids, images_clip, extras):
+        """One prompt planned and spliced -> (its input embeddings [1, S, d], S)."""
         cfg, dev, llm = self.config, self.device_, self.model.llm
         plan, feats = self._encode_and_plan(ids, None, None, images_clip, extras.mask_images, extras.image_token_types, extras.image_token_lengths,
                                             with_seg=False, region_masks=extras.region_masks if extras.region_masks else None,
                                             valid_region_masks_bool=extras.valid_region_masks_bool)
         src = _h2d(plan.src_code.reshape(-1), dev)
         S = plan.seq_len
-        embeds = ops.splice_rows(llm.embed_tokens, feats, src, cfg.hidden_size).view(1, S, cfg.hidden_size)
+        return ops.splice_rows(llm.embed_tokens, feats, src, cfg.hidden_size).view(1, S, cfg.hidden_size), S
+
+    def _prefill_batch(self, prompts, max_new_tokens):
+        """The prompts of a batch group — (ids, images_clip, extras) each — planned first, then each prefilled at batch 1 (the bits of
+        generate()'s prefill) into its own row of ONE KV cache of len(prompts) rows and max(S_b) + max_new_tokens positions, allocated before
+        the first prefill so that the RoPE tables have grown before anything is captured.  -> ([hidden per row], cache, [S_b])."""
+        llm = self.model.llm
+        planned = [self._plan_embeds(*p) for p in prompts]
+        lengths = [S for _, S in planned]
+        cache = llm.new_kv_cache(len(prompts), max(lengths) + max_new_tokens)
+        hiddens = []
+        for b, (embeds, S) in enumerate(planned):
+            row = {"len": 0, "k": [t[b:b + 1] for t in cache["k"]], "v": [t[b:b + 1] for t in cache["v"]], "err": cache["err"]}
+            hiddens.append(llm.forward(embeds, None, kv_cache=row)[0])
+        cache["len"] = max(lengths)
+        return hiddens, cache, lengths
+
+    def _prefill(self, ids, images_clip, extras, max_new_tokens, rows=1):
+        """The spliced prompt through the stack at batch 1, into row 0 of a KV cache of `rows` rows and S + max_new_tokens positions (allocated
+        here, so the RoPE tables have grown before anything is captured); the prompt's K/V copied to the other rows.  -> (hidden, cache, S)."""
+        llm = self.model.llm
+        embeds, S = self._plan_embeds(ids, images_clip, extras)
         cache = llm.new_kv_cache(rows, S + max_new_tokens)
         row0 = cache if rows == 1 else {"len": 0, "k": [t[:1] for t in cache["k"]], "v": [t[:1] for t in cache["v"]], "err": cache["err"]}
         hidden, _, _ = llm.forward(embeds, None, kv_cache=row0)
@@ -459,10 +603,11 @@ class GenerationMixin:
         return hidden, cache, S
 
     def _drive(self, policy, hidden, cache, S, max_new_tokens, captured, looks=None):
-        """The steps of one call after its prefill: step 0 from the prefill's last position, then the captured graph or the loop.  A generator
-        of what the policy yields: at `looks` (default: _default_looks) when captured, after every token in the loop."""
+        """The steps of one call after its prefill: step 0 from the prefill's last position (hidden [1, S, d]; a batch group: the rows' last
+        positions [B, d]), then the captured graph or the loop.  A generator of what the policy yields: at `looks` (default: _default_looks)
+        when captured, after every token in the loop."""
         llm = self.model.llm
-        policy.first(llm.next_token_logits(hidden[0, -1:]))
+        policy.first(llm.next_token_logits(hidden[0, -1:] if hidden.dim() == 3 else hidden))
         policy.file(0)
         self.last_decode_path = "graph" if captured else "loop"
         if captured:
@@ -479,6 +624,17 @@ class GenerationMixin:
         captured = self._captures(max_new_tokens) and not host_pick
         policy = _single_row_policy(self.model.llm, hidden, cache, max_new_tokens, stop_ids, pick, debug, captured)
         yield from self._drive(policy, hidden, cache, S, max_new_tokens, captured, looks)
+
+    def _decode_batch(self, prompts, max_new_tokens, stop_ids, pick=_argmax_pick, looks=None, debug=None):
+        """_decode for the prompts of one batch group, (ids, images_clip, extras) each, as the rows of one decode step (_batch_policy): every
+        prompt prefilled at batch 1 into its row of one cache, then single-token steps at B rows with a position and a key count per row,
+        the next tokens chosen by `pick` over the [B, V] logits.  Through the captured graph under _decode's conditions, else token by token.
+        A generator of ([generated ids so far per row], [stopped per row], [[hidden states of the prompt, of each fed token] per row])."""
+        hiddens, cache, lengths = self._prefill_batch(prompts, max_new_tokens)
+        captured = self._captures(max_new_tokens)
+        policy = _batch_policy(self.model.llm, hiddens, cache, lengths, max_new_tokens, stop_ids, pick, debug, captured)
+        last = torch.cat([h[0, -1:] for h in hiddens])
+        yield from self._drive(policy, last, cache, lengths, max_new_tokens, captured, looks)      # (S: the error message's positions, per row)
 
     def _greedy(self, ids, images_clip, max_new_tokens, eos_token_id, extras=NO_EXTRAS, pick=_argmax_pick):
         """HF `generate(do_sample=False, use_cache=True)` on one sample (MedPLIB.py:592-606; prepare_inputs_for_generation,
@@ -508,20 +664,8 @@ class GenerationMixin:
         rows = []
         with self._decoding(who):
             for b in range(ids.shape[0]):
-                row = ids[b:b + 1]
-                if attention_mask is not None:
-                    row = row[:, _np_ids(attention_mask)[b].astype(bool)]               # drop this row's padding
-                img = images[b] if isinstance(images, (list, tuple)) else images[b:b + 1]
-                if isinstance(images, (list, tuple)):
-                    img = [img]
-                rm, rv = kwargs.get("region_masks") or (), kwargs.get("valid_region_masks_bool") or ()
-                if len(rm) > 0:            # the collator's flat list holds one entry per sample WITH regions: pick this row's
-                    before = sum(1 for v in rv[:b] if any(v))
-                    rm, rv = (rm[before:before + 1] if any(rv[b]) else ()), rv[b:b + 1]
-                extras = PromptExtras(kwargs.get("mask_images"), kwargs.get("image_token_types"), kwargs.get("image_token_lengths"), rm, rv)
-                rows.append(decode_row(b, row, img, extras)[0])
-        n = max(r.shape[0] for r in rows)
-        return torch.from_numpy(np.stack([np.concatenate([r, np.full(n - r.shape[0], eos_token_id, np.int64)]) for r in rows]))
+                rows.append(decode_row(b, *_row_prompt(ids, images, attention_mask, kwargs, b))[0])
+        return _padded_rows(rows, eos_token_id)
 
     @torch.no_grad()
     def generate(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, **kwargs):
@@ -533,6 +677,48 @@ class GenerationMixin:
         _check_kwargs("generate", kwargs)
         return self._generate_rows("generate", input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs,
                                    lambda b, row, img, extras: self._greedy(row, img, max_new_tokens, eos_token_id, extras)[0])
+
+    @torch.no_grad()
+    def generate_batch(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, batch_rows=8, **kwargs):
+        """generate() with the prompts decoded TOGETHER: the rows are taken in groups of `batch_rows` (1..8, else ValueError) and the prompts
+        of a group — whatever their lengths — are the rows of one decode step, so a group pays one pass over the decoder weights per token
+        instead of one per prompt (_decode_batch, _batch_policy).  Each prompt is prefilled at batch 1 as in generate(); a row stops at its
+        own eos (what the step computes for it afterwards is discarded) and a group is done when every row has stopped or at max_new_tokens.
+        A MoE layer routes every row as generate() does (capacity = the rows of the group, no draws): no row is dropped because of its
+        batch-mates, so a row's answer does not depend on the others; it is generate()'s function in another summation order (the narrow
+        projections of one row take the K-split form, of several the shared one), not its bits.  Same return layout as generate(): prompt
+        included, right-padded with eos.  batch_rows = 8: the shared GEMV reads the weights once for up to four rows and twice for five to
+        eight, and eight rows still gave more tokens per second than four on the dense and on the MoE model at 7B (profiles/batch_decode.md:
+        +10 % and +13 %; four rows are the better latency).  Refused: sampling (generate_sample) and beams (generate_beam) per row, and — NotImplementedError
+        before any state changes — gate sampling or an injected draw provider, the residual MoE and expert parallelism.  Not built: batched
+        prefill, evaluate() / <SEG> masks per batch."""
+        _check_kwargs("generate_batch", kwargs)
+        n_rows, max_new_tokens = int(batch_rows), int(max_new_tokens)
+        if not 1 <= n_rows <= 8:
+            raise ValueError(f"generate_batch(): batch_rows={batch_rows} must lie in 1..8 (the rows of one decode step)")
+        assert max_new_tokens >= 1
+        why = self.model.llm.batch_rows_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"generate_batch(): {why}: call generate()")
+        return self._generate_groups(input_ids, images, attention_mask, max_new_tokens, eos_token_id, n_rows, kwargs, _argmax_pick)
+
+    @torch.no_grad()
+    def _generate_groups(self, input_ids, images, attention_mask, max_new_tokens, eos_token_id, n_rows, kwargs, pick):
+        """generate_batch() behind its argument checks: the rows in groups of n_rows through _decode_batch, the next tokens chosen by
+        pick(logits [B, V], step) -> int64 [B]; output ids [B, L + n_max], prompt included, right-padded with eos."""
+        ids = _np_ids(input_ids).astype(np.int64)
+        rows = []
+        with self._decoding("generate_batch"):
+            prompts = [_row_prompt(ids, images, attention_mask, kwargs, b) for b in range(ids.shape[0])]
+            for g0 in range(0, len(prompts), n_rows):
+                group = prompts[g0:g0 + n_rows]
+                generated = [[] for _ in group]
+                # (closed before the prologue is undone: the driver's `finally` settles the pass counter)
+                with contextlib.closing(self._decode_batch(group, max_new_tokens, (eos_token_id,), pick=pick)) as steps:
+                    for generated, _, _ in steps:
+                        pass
+                rows += [np.concatenate([p[0][0], np.asarray(g, dtype=np.int64)]) for p, g in zip(group, generated)]
+        return _padded_rows(rows, eos_token_id)
 
     @torch.no_grad()
     def generate_sample(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, temperature=1.0, top_k=50,

@@ -7,6 +7,7 @@ Weights are held in kernel layout (fused qkv [3d,d], gate/up fused [2ff,d] with 
 SwiGLU-in-epilogue GEMM, experts stacked [E,...]) and are
 imported from / exported to the HF checkpoint key layout by load_hf / export_hf."""
 import math
+import os
 
 import torch
 
@@ -19,6 +20,10 @@ def _rope_tables(seq, head_dim, theta, device, start=0):
     freqs = torch.outer(torch.arange(start, seq, dtype=torch.float32), inv)
     return freqs.cos().contiguous().to(device), freqs.sin().contiguous().to(device)
 
+
+# MP_GEMV_GROUPED=0: the ragged batch rows of a top-1 MoE layer keep the indexed expert GEMVs (one weight stream per row) instead of the grouped
+# form (one per expert): an A/B switch, read once; LlamaStack.group_expert_gemvs starts from it
+GEMV_GROUPED = os.environ.get("MP_GEMV_GROUPED", "1") != "0"
 
 ROPE_GROW_ROWS = 1024     # RoPE tables grow in whole multiples of this many rows (slowly lengthening prompts do not reallocate each call)
 
@@ -76,6 +81,7 @@ class LlamaStack:
         self._draws_all = None             # fp32 [L * T * E] gate draws of one pass, all layers: _gate_draws writes and slices
         self.fuse_moe_gather_scatter = True   # top-1, one rank: dispatch / combine folded into the expert GEMMs
         self.fuse_decode_routing = True       # decode rows: post-attention norm + gate + routing in one launch
+        self.group_expert_gemvs = GEMV_GROUPED   # ragged batch rows, top-1, bf16: one weight pass per expert (ops.gemv_grouped), else the indexed form
         self.w8 = None                     # 8-bit decode mode: per layer {"qkv" | "o" | "gu" | "down": (codes, scale)}, or None (off): quantize_decode_weights / drop_decode_weights_w8
         self.w8_epoch = None               # ops.PARAM_EPOCH the copies were quantised at
         self.w4 = None                     # 4-bit decode mode: per layer {"qkv" | "o" | "gu" | "down": (codes, absmax)}, or None (off): quantize_decode_weights_nf4 / drop_decode_weights_w4; never set together with w8
@@ -284,9 +290,14 @@ class LlamaStack:
         """Whether T rows of a MoE layer take the per-row expert GEMVs (the decode rows): one rank, at most 8 rows, no residual MoE."""
         return self.ep is None and T <= 8 and not self.cfg.use_residual
 
-    def _expert_gemvs_top1(self, lw, h, x, expert, slot, weight, q8=None):
+    def _expert_gemvs_top1(self, lw, h, x, expert, slot, weight, q8=None, grouped=False):
         """Decode rows, top-1: each row streams its own expert's matrices (GEMV with a device-side expert index); the combine weight, the
-        capacity drop and the residual ride in the down projection's epilogue.  Behind _mlp's routing and behind decode_step's fused one."""
+        capacity drop and the residual ride in the down projection's epilogue.  Behind _mlp's routing and behind decode_step's fused one.
+        grouped (the ragged rows of a batch, bf16 weights): the rows that name the same expert share its weight pass (ops.gemv_grouped: the
+        indexed form's bits); group_expert_gemvs = False keeps the indexed form (A/B)."""
+        if grouped and q8 is None and self.group_expert_gemvs:
+            act = ops.gemv_grouped(h, lw["gu"], expert, act=ops.ACT_SWIGLU_PAIR, row_keep=slot)
+            return ops.gemv_grouped(act, lw["down"], expert, residual=x, row_scale=weight, row_keep=slot)
         if q8 is not None:         # (the 8-bit and NF4 gate|up also skip a dropped row's weights; its act row stays unwritten and the down projection never reads it)
             act = self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR, w_index=expert, row_keep=slot)
         else:                      # (the bf16 kernel would skip it too, given row_keep; the recorded launch traces pin this call without it)
@@ -299,23 +310,24 @@ class LlamaStack:
         act = ops.gemv_top2_gate_up(h, lw["gu"], expert, slot)
         return ops.gemv_top2_down(act, lw["down"], expert, slot, weight, x)
 
-    def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None, pass_dev=None, q8=None):
+    def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None, pass_dev=None, q8=None, cap=None):
         """x + MLP(h): h = post-attention RMSNorm output [T,d], x = residual stream [T,d]; gate = (logits, gates) when the caller's fused
         norm kernel already produced them (ops.rmsnorm_gate); needed = (rows, mask) when only those output rows are read (the last layer);
-        rstd: the folded post-attention norm (h is None then); q8: the layer's 8-bit or NF4 copies when the rows are decode rows.  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
+        rstd: the folded post-attention norm (h is None then); q8: the layer's 8-bit or NF4 copies when the rows are decode rows; cap: the ragged rows of a batch (decode_step with `rows`) — that capacity (T: nothing dropped), no draws, the grouped expert GEMVs.  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
         cfg, T = self.cfg, x.shape[0]
         if i not in self.moe_layers:
             if T <= 8:
                 return self._row_proj(lw, "down", self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR), q8, residual=x), None, None
             act = ops.gemm(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR)       # silu(gate)*up fused into the GEMM epilogue
             return ops.gemm(act, lw["down"], residual=x), None, None
-        E, k, cap = cfg.num_experts, cfg.top_k_experts, self.capacity(T)
+        ragged = cap is not None
+        E, k, cap = cfg.num_experts, cfg.top_k_experts, cap if ragged else self.capacity(T)
         logits, gates = gate if gate is not None else ops.moe_gate(h, lw["wg"])
         if k == 1 and self._expert_gemv_rows(T):
             # (no gate draws: random token selection only acts when an expert is over capacity; below cap >= T the draws are generated as usual)
             draws = None if cap >= T else self._gate_draws(i, T, E, False, pass_dev)
             expert, slot, weight, kept, counts, l_aux = ops.moe_route_top1(gates, cap, draws)
-            return self._expert_gemvs_top1(lw, h, x, expert, slot, weight, q8), l_aux, (expert, slot, counts)
+            return self._expert_gemvs_top1(lw, h, x, expert, slot, weight, q8, grouped=ragged), l_aux, (expert, slot, counts)
         if k == 2 and self._expert_gemv_rows(T):
             expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2(gates, logits, cap, self._gate_draws(i, T, E, True, pass_dev))
             return self._expert_gemvs_top2(lw, h, x, expert, slot, weight), l_aux, (expert, slot, counts)
@@ -513,11 +525,29 @@ class LlamaStack:
             self.last_gate_inputs = gate_inputs            # per MoE layer: the residual stream in front of the post-attention norm (oracle/parity.py)
         return out.view(B, S, d), aux, (routing if collect_routing else None)
 
-    def decode_step(self, emb, kv_cache, counters, pass_dev=None):
+    def batch_rows_unsupported(self):
+        """Why this stack cannot decode ragged batch rows (decode_step with `rows`; generate_batch), a sentence, or None.  A row of a batch is
+        routed as generate() routes it (T = 1: nothing dropped, no draws), so what needs the other rows or a draw is refused."""
+        cfg = self.cfg
+        if cfg.moe_gate_sampling or self.rts_uniform_provider is not None:
+            return "the gate's random draws (moe_gate_sampling / an injected draw provider) are keyed on the rows of one pass"
+        if cfg.use_residual:
+            return "the residual MoE (use_residual) decodes through the GEMM path, which drops rows by the batch's capacity"
+        if self.ep is not None:
+            return "expert parallelism routes through the capacity slabs of the expert-parallel group"
+        return None
+
+    def decode_step(self, emb, kv_cache, counters, pass_dev=None, rows=None):
         """One token per sequence against the KV cache with the cache length held ON THE DEVICE (`counters` int32 [2] =
         [position of the new token, number of valid keys after appending it]): no launch argument depends on the step, so the
         whole step can be captured once into a HIP graph and replayed per token (evaluate()).  emb [B, 1, d] -> hidden [B, 1, d].
         The caller advances `counters` (ops.advance_ints) after the step.
+        rows = (position int32 [B], keys int32 [B]) in place of `counters` (None then): every sequence has its OWN length — the ragged prompts
+        of generate_batch as the rows of one step.  The layer body then takes the unfused qkv branch (the norm-folded launches have no per-row
+        twin), ops.decode_rope_append_rows and ops.attention_decode_rows, and routes a MoE layer's rows with a capacity of B and no draws (no
+        row is dropped because of its batch-mates: a row's answer does not depend on the others); a top-1 layer's rows share one weight pass
+        per expert (ops.gemv_grouped; the 8-bit and NF4 copies keep the indexed form).  NotImplementedError before any state changes where
+        batch_rows_unsupported() says so.
         Reproducibility note (round-4 advisor): the narrow projections (o_proj, down) take the K-split GEMV when B == 1 or an expert index is
         given and the shared-weight form otherwise; the two add their partial dot products in different orders, so the SAME prompt decoded at
         batch 1 and at batch 2 may differ in the last fp32 bit of those projections (and, at a near-tie of two logits, in a greedy token).
@@ -526,13 +556,19 @@ class LlamaStack:
         (moe_gate_sampling) instead of the host counter `gate_pass` — a captured step then draws, at every replay, what the token-by-token
         loop draws for that pass; the caller advances it with the counters."""
         cfg = self.cfg
+        ragged = rows is not None
+        if ragged:
+            why = self.batch_rows_unsupported()
+            if why is not None:
+                raise NotImplementedError(f"decode_step with per-row lengths: {why}")
+            pos_rows, key_rows = rows
         B, _, d = emb.shape
         H, D, E, k = cfg.num_attention_heads, cfg.head_dim, cfg.num_experts, cfg.top_k_experts
         x = emb.reshape(B, d)
         self.gate_pass += 1
-        # input_layernorm inside the qkv GEMV (same bits, one launch less per layer); the norm-folded launches have no 8-bit or NF4 twins: those modes
-        # take the unfused branches
-        fold = self.w8 is None and self.w4 is None and ops.gemv_rmsnorm_ok(B, d, head_dim=D, swiglu_n=2 * cfg.intermediate_size)
+        # input_layernorm inside the qkv GEMV (same bits, one launch less per layer); the norm-folded launches have no 8-bit or NF4 twins and no
+        # per-row twin: those modes take the unfused branches
+        fold = not ragged and self.w8 is None and self.w4 is None and ops.gemv_rmsnorm_ok(B, d, head_dim=D, swiglu_n=2 * cfg.intermediate_size)
         for i, lw in enumerate(self.layers):
             q8 = self._decode_copies(i)
             if fold:                                            # norm + projection + RoPE + cache append: one launch, the three launches' bits
@@ -540,17 +576,23 @@ class LlamaStack:
                                                    kv_cache["v"][i], counters[0:1], H, D, err=kv_cache["err"])
             else:
                 qkv = self._row_proj(lw, "qkv", ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps), q8)
-                ops.decode_rope_append(qkv, self.cos, self.sin, kv_cache["k"][i], kv_cache["v"][i], counters[0:1], H, D, err=kv_cache["err"])
+                if ragged:
+                    ops.decode_rope_append_rows(qkv, self.cos, self.sin, kv_cache["k"][i], kv_cache["v"][i], pos_rows, H, D, err=kv_cache["err"])
+                else:
+                    ops.decode_rope_append(qkv, self.cos, self.sin, kv_cache["k"][i], kv_cache["v"][i], counters[0:1], H, D, err=kv_cache["err"])
             q4 = qkv.view(B, 1, 3, H, D)[:, :, 0]
-            attn = ops.attention(q4, kv_cache["k"][i], kv_cache["v"][i], causal=False, sk_dev=counters[1:2])
+            if ragged:
+                attn = ops.attention_decode_rows(q4, kv_cache["k"][i], kv_cache["v"][i], key_rows)
+            else:
+                attn = ops.attention(q4, kv_cache["k"][i], kv_cache["v"][i], causal=False, sk_dev=counters[1:2])
             x = self._row_proj(lw, "o", attn.view(B, d), q8, residual=x)
             # post-attention norm + gate + routing in ONE launch, then the expert GEMVs of _mlp's decode-row branches (the separate kernels' bits)
             if i in self.moe_layers and self.fuse_decode_routing and self._expert_gemv_rows(B) and k in (1, 2):
-                cap = self.capacity(B)
+                cap = B if ragged else self.capacity(B)         # (ragged rows: generate()'s routing of each row, where nothing can be dropped)
                 if k == 1:
                     draws = None if cap >= B else self._gate_draws(i, B, E, False, pass_dev)
                     h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
-                    x = self._expert_gemvs_top1(lw, h, x, expert, slot, weight, q8)
+                    x = self._expert_gemvs_top1(lw, h, x, expert, slot, weight, q8, grouped=ragged)
                 else:
                     draws = self._gate_draws(i, B, E, True, pass_dev)
                     h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route_top2(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
@@ -560,7 +602,7 @@ class LlamaStack:
                 act = ops.gemv_rmsnorm(x, lw["ln2"], cfg.rms_norm_eps, lw["gu"], act=ops.ACT_SWIGLU_PAIR)
                 x = ops.gemv(act, lw["down"], residual=x)
             else:
-                x, _, _ = self._mlp(i, lw, ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps), x, pass_dev=pass_dev, q8=q8)
+                x, _, _ = self._mlp(i, lw, ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps), x, pass_dev=pass_dev, q8=q8, cap=B if ragged else None)
         return ops.rmsnorm(x, self.norm_w, cfg.rms_norm_eps).view(B, 1, d)
 
     def next_token_logits(self, hidden_row):

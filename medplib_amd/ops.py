@@ -329,6 +329,32 @@ def gemv(x, w, bias=None, residual=None, act=ACT_NONE, out_dtype=torch.bfloat16,
     return out
 
 
+def gemv_grouped(x, w, w_index, residual=None, act=ACT_NONE, row_scale=None, row_keep=None, out=None):
+    """gemv(x, w, w_index=...) with one weight stream per expert instead of one per row (mp_gemv_grouped_bf16): x [M <= 8, K] bf16, w [E, N, K]
+    bf16, w_index int32 [M] on the device; the rows that name the same expert share its weight pass.  Row for row the bits of gemv() with
+    the same arguments.  act ACT_NONE (with residual / row_scale / row_keep as gemv) or ACT_SWIGLU_PAIR; bf16 output.  out (tests): a
+    pre-filled output to write into."""
+    _chk(x, torch.bfloat16, "gemv_grouped.x"); _chk(w, torch.bfloat16, "gemv_grouped.w"); _chk(w_index, torch.int32, "gemv_grouped.w_index")
+    M, K = x.shape
+    assert w.dim() == 3 and w.shape[2] == K and x.stride(1) == 1 and w.stride(-1) == 1 and w_index.shape == (M,) and w_index.stride(0) == 1
+    E, N = w.shape[0], w.shape[1]
+    for t, dt, n in ((row_scale, torch.float32, "row_scale"), (row_keep, torch.int32, "row_keep")):
+        if t is not None:
+            _chk(t, dt, "gemv_grouped." + n)
+            assert t.shape == (M,) and t.stride(0) == 1
+    if residual is not None:
+        _chk(residual, torch.bfloat16, "gemv_grouped.residual")
+        assert residual.shape == (M, N) and residual.stride(1) == 1
+    cols = N // 2 if act == ACT_SWIGLU_PAIR else N
+    if out is None:
+        out = torch.empty((M, cols), dtype=torch.bfloat16, device=x.device)
+    _chk(out, torch.bfloat16, "gemv_grouped.out")
+    assert out.shape[0] >= M and out.shape[1] >= cols and out.stride(1) == 1
+    lib().call("mp_gemv_grouped_bf16", _p(x), x.stride(0), _p(w), w.stride(1), w.stride(0), _p(out), out.stride(0), _p(residual),
+               residual.stride(0) if residual is not None else 0, _p(w_index), _p(row_scale), _p(row_keep), M, N, K, E, act, _stream())
+    return out
+
+
 def quantize_rows_w8(w):
     """Row-wise absmax 8-bit copy of a projection (bitsandbytes' weight format): w [N, K] or [E, N, K] bf16 -> (codes int8 of w's shape,
     scale fp32 [N] or [E, N]) with scale = absmax / 127 and codes = rint(w * (127 / absmax)) per output row; a zero row gets scale 0."""
@@ -444,6 +470,25 @@ def attention(q, k, v, out=None, causal=False, key_valid=None, rel_h=None, rel_w
     lib().call("mp_attention_fwd_bf16", _p(q), q.stride(0), q.stride(1), _p(k), k.stride(0), k.stride(1), _p(v), v.stride(0),
                v.stride(1), _p(out), out.stride(0), out.stride(1), _p(key_valid), _p(rel_h), _p(rel_w), kh, kw, B, H, Sq, Sk,
                D, int(causal), float(scale), variant, _p(sk_dev), _stream())
+    return out
+
+
+def attention_decode_rows(q, k, v, sk_dev, out=None, scale=None):
+    """The single-query decode step over ragged batch rows: q [B, 1, H, D], k / v [B, Sk, H, D] bf16 views as attention() takes them, sk_dev
+    int32 [B] on the device: row b attends to its first min(Sk, sk_dev[b]) keys.  Returns [B, 1, H*D] bf16.  Row b has the bits of
+    attention(q, k, v, sk_dev=<[sk_dev[b]]>) on the same tensors (mp_attention_decode_rows_bf16)."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _chk(t, torch.bfloat16, "attention_decode_rows." + n)
+        assert t.dim() == 4 and t.stride(3) == 1 and t.stride(2) == t.shape[3]
+    _chk(sk_dev, torch.int32, "attention_decode_rows.sk_dev")
+    B, Sq, H, D = q.shape
+    assert Sq == 1 and k.shape[0] == B and v.shape == k.shape and sk_dev.shape == (B,) and sk_dev.stride(0) == 1
+    if out is None:
+        out = torch.empty((B, 1, H * D), dtype=torch.bfloat16, device=q.device)
+    assert out.shape == (B, 1, H * D) and out.stride(2) == 1
+    _ensure_gemm_workspace(q.device)              # the decode kernel splits a head's keys over workgroups through this scratch
+    lib().call("mp_attention_decode_rows_bf16", _p(q), q.stride(0), _p(k), k.stride(0), k.stride(1), _p(v), v.stride(0), v.stride(1), _p(out),
+               out.stride(0), _p(sk_dev), B, H, k.shape[1], D, float(D ** -0.5 if scale is None else scale), _stream())
     return out
 
 
@@ -872,6 +917,18 @@ def decode_rope_append(qkv, cos_t, sin_t, cache_k, cache_v, pos_dev, heads, head
     assert qkv.dim() == 2 and qkv.stride(1) == 1 and cache_k.stride(3) == 1 and cache_k.stride(2) == head_dim
     table_rows, cache_rows, err = _decode_bounds(cos_t, sin_t, cache_k, cache_v, err)
     lib().call("mp_decode_rope_append_bounded_bf16", _p(qkv), qkv.stride(0), _p(cos_t), _p(sin_t), _p(cache_k), _p(cache_v), _p(pos_dev),
+               qkv.shape[0], heads, head_dim, cache_k.stride(0), cache_k.stride(1), table_rows, cache_rows, _p(err), _stream())
+
+
+def decode_rope_append_rows(qkv, cos_t, sin_t, cache_k, cache_v, pos_dev, heads, head_dim, err=None):
+    """decode_rope_append with a position per sequence (the ragged rows of generate_batch): pos_dev int32 [B] on the device, row b rotated at
+    pos_dev[b] and appended to cache[b, pos_dev[b]].  Bounded per row (mp_decode_rope_append_rows_bounded_bf16): a row whose position has no
+    table or cache row writes nothing and ORs MP_POS_ERR_* into `err`; the other rows are unaffected."""
+    _chk(qkv, torch.bfloat16, "decode_rope_append_rows.qkv"); _chk(pos_dev, torch.int32, "decode_rope_append_rows.pos")
+    assert qkv.dim() == 2 and qkv.stride(1) == 1 and cache_k.stride(3) == 1 and cache_k.stride(2) == head_dim
+    assert pos_dev.shape == (qkv.shape[0],) and pos_dev.stride(0) == 1 and cache_k.shape[0] >= qkv.shape[0]
+    table_rows, cache_rows, err = _decode_bounds(cos_t, sin_t, cache_k, cache_v, err)
+    lib().call("mp_decode_rope_append_rows_bounded_bf16", _p(qkv), qkv.stride(0), _p(cos_t), _p(sin_t), _p(cache_k), _p(cache_v), _p(pos_dev),
                qkv.shape[0], heads, head_dim, cache_k.stride(0), cache_k.stride(1), table_rows, cache_rows, _p(err), _stream())
 
 
