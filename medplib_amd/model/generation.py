@@ -468,8 +468,7 @@ class GenerationMixin:
         written since they were made.  Yields the ExitStack that holds the merge: close() it to have the plain weights back before the block ends."""
         self._require_shadowable(who)
         self.sync_side_streams()
-        self._refresh_decode_8bit(who)
-        self._refresh_decode_4bit(who)
+        self._refresh_decode_weights(who)
         was_training = self.training
         self.train(False)
         try:
@@ -479,11 +478,43 @@ class GenerationMixin:
         finally:
             self.train(was_training)
 
+    # ------------------------------------------------------------------ quantised decode weights (llama.DECODE_MODES): one helper set under the public pairs
+    def _decode_bits_on(self, bits):
+        """Whether the decode steps stream the copies of mode `bits`."""
+        dw = self.model.llm.decode_weights
+        return dw is not None and dw.mode.bits == bits
+
+    def _enable_decode_weights(self, bits, on):
+        """enable_decode_<bits>bit(on): off drops the copies only when this mode is the one that is on; on (re-)quantises, which drops the
+        other mode's copies."""
+        llm = self.model.llm
+        if not on:
+            if self._decode_bits_on(bits):
+                llm.drop_decode_weights()
+            return self
+        self._refuse_in_shadow(f"enable_decode_{bits}bit")
+        self.sync_side_streams()
+        llm.quantize_decode_weights(bits)
+        return self
+
+    def _refresh_decode_weights(self, who):
+        """The decode prologue's part in a quantised mode: what enabling it refuses may have been attached since (adapters, expert parallelism),
+        and an optimizer step or a checkpoint load (ops.PARAM_EPOCH) leaves the copies stale."""
+        llm = self.model.llm
+        if llm.decode_weights is None:
+            return
+        mode = llm.decode_weights.mode
+        why = llm.decode_weights_unsupported(mode.bits)
+        if why is not None:
+            raise NotImplementedError(f"{who}() in {mode.words} decode mode: {why} (or enable_decode_{mode.bits}bit(False))")
+        if llm.decode_weights.epoch != ops.PARAM_EPOCH:
+            llm.quantize_decode_weights(mode.bits)
+
     # ------------------------------------------------------------------ 8-bit decode weights (the reference worker's --load-8bit)
     @property
     def decode_8bit(self):
         """Whether the decode steps stream the 8-bit copies of the decoder projections."""
-        return self.model.llm.w8 is not None
+        return self._decode_bits_on(8)
 
     def enable_decode_8bit(self, on=True):
         """The reference worker's --load-8bit (model/serve/model_worker.py:72,100,642 -> builder.py:39, bitsandbytes) as a SPEED mode of the
@@ -495,62 +526,25 @@ class GenerationMixin:
         routing, the residual MoE, expert parallelism, attached adapters (merge_and_unload() first) and dimensions that are no multiple of 16.
         enable_decode_8bit(False) drops the copies: today's path, bit for bit.  Exclusive with enable_decode_4bit: enabling one mode drops the
         other's copies."""
-        llm = self.model.llm
-        if not on:
-            llm.drop_decode_weights_w8()
-            return self
-        self._refuse_in_shadow("enable_decode_8bit")
-        self.sync_side_streams()
-        llm.quantize_decode_weights()
-        return self
-
-    def _refresh_decode_8bit(self, who):
-        """The decode prologue's part in 8-bit mode: what enable_decode_8bit refuses may have been attached since (adapters, expert parallelism),
-        and an optimizer step or a checkpoint load (ops.PARAM_EPOCH) leaves the copies stale."""
-        llm = self.model.llm
-        if llm.w8 is None:
-            return
-        why = llm.decode_w8_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"{who}() in 8-bit decode mode: {why} (or enable_decode_8bit(False))")
-        if llm.w8_epoch != ops.PARAM_EPOCH:
-            llm.quantize_decode_weights()
+        return self._enable_decode_weights(8, on)
 
     # ------------------------------------------------------------------ 4-bit NF4 decode weights (the reference's load_in_4bit, nf4)
     @property
     def decode_4bit(self):
         """Whether the decode steps stream the NF4 copies of the decoder projections."""
-        return self.model.llm.w4 is not None
+        return self._decode_bits_on(4)
 
     def enable_decode_4bit(self, on=True):
         """The reference's load_in_4bit with bnb_4bit_quant_type="nf4" (model/builder.py:41-47, chat.py:89-98; bitsandbytes) as a SPEED mode of
         the decode steps, like enable_decode_8bit and exclusive with it (enabling one drops the other's copies): NF4 copies of the decoder's
         qkv, o, gate|up and down projections — 4-bit codes into QLoRA's table with one fp32 absmax per 64 weights, 0.5625 bytes per weight
-        (LlamaStack.quantize_decode_weights_nf4) — are added beside the bf16 weights, and every single-token decode step of evaluate / generate
+        (LlamaStack.quantize_decode_weights) — are added beside the bf16 weights, and every single-token decode step of evaluate / generate
         / generate_sample / generate_beam / generate_stream, captured or looped, streams them.  The absmax stays fp32 (no double
         quantisation), the table is NF4 only (no fp4), and the GEMV multiplies with the table rounded to bf16.  Prefill, training and export
         keep the bf16 weights and their bits; lm_head, the embeddings, the norms and the MoE gate stay as they are.  NotImplementedError, with
         the mode left as it was, for top-2 routing, the residual MoE, expert parallelism, attached adapters (merge_and_unload() first) and
         dimensions that are no multiple of 64.  enable_decode_4bit(False) drops the copies: today's path, bit for bit."""
-        llm = self.model.llm
-        if not on:
-            llm.drop_decode_weights_w4()
-            return self
-        self._refuse_in_shadow("enable_decode_4bit")
-        self.sync_side_streams()
-        llm.quantize_decode_weights_nf4()
-        return self
-
-    def _refresh_decode_4bit(self, who):
-        """_refresh_decode_8bit for the NF4 copies."""
-        llm = self.model.llm
-        if llm.w4 is None:
-            return
-        why = llm.decode_w4_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"{who}() in 4-bit decode mode: {why} (or enable_decode_4bit(False))")
-        if llm.w4_epoch != ops.PARAM_EPOCH:
-            llm.quantize_decode_weights_nf4()
+        return self._enable_decode_weights(4, on)
 
     def _graph_decode_ok(self):
         """Whether the captured step computes what the token-by-token loop computes for this model: top-1, or top-2 on one rank without the

@@ -6,6 +6,7 @@ medplib_moe_llama.py:110-305) and HF-4.31 LlamaAttention/LlamaMLP/LlamaRMSNorm (
 Weights are held in kernel layout (fused qkv [3d,d], gate/up fused [2ff,d] with rows interleaved in blocks of 32 for the
 SwiGLU-in-epilogue GEMM, experts stacked [E,...]) and are
 imported from / exported to the HF checkpoint key layout by load_hf / export_hf."""
+import collections
 import math
 import os
 
@@ -31,6 +32,18 @@ ROPE_GROW_ROWS = 1024     # RoPE tables grow in whole multiples of this many row
 def rope_rows_for(n, rows):
     """Rows a RoPE table of `rows` rows must have to cover positions 0 .. n - 1: unchanged when it does, else n rounded up to ROPE_GROW_ROWS."""
     return rows if n <= rows else -(-n // ROPE_GROW_ROWS) * ROPE_GROW_ROWS
+
+
+# THE table of quantised decode modes, keyed by bit width: what a decode row streams in place of the bf16 weights.  words: the mode in messages;
+# quantizer / gemv: NAMES of ops functions, resolved at call time (tests count calls by patching them on the module); multiple / why: what
+# hidden_size and intermediate_size must be multiples of.  A further mode is one entry here, its ops pair and its pair of public wrappers
+# (generation.GenerationMixin); nothing else in this file or that one names a bit width.
+DecodeMode = collections.namedtuple("DecodeMode", "bits words quantizer gemv multiple why")
+DECODE_MODES = {m.bits: m for m in (
+    DecodeMode(8, "8-bit", "quantize_rows_w8", "gemv_w8", 16, "16 codes per 16-byte load"),            # row-wise absmax int8, bitsandbytes' weight format: (codes, scale), + half the decoder's bf16 bytes
+    DecodeMode(4, "4-bit", "quantize_blocks_nf4", "gemv_w4", 64, "one absmax per block of 64 weights"),  # NF4: 4-bit codes, one fp32 absmax per 64 weights: (codes, absmax), + 0.28 of them
+)}
+DecodeWeights = collections.namedtuple("DecodeWeights", "mode copies epoch")    # LlamaStack.decode_weights while a mode is on
 
 
 class LlamaStack:
@@ -82,10 +95,7 @@ class LlamaStack:
         self.fuse_moe_gather_scatter = True   # top-1, one rank: dispatch / combine folded into the expert GEMMs
         self.fuse_decode_routing = True       # decode rows: post-attention norm + gate + routing in one launch
         self.group_expert_gemvs = GEMV_GROUPED   # ragged batch rows, top-1, bf16: one weight pass per expert (ops.gemv_grouped), else the indexed form
-        self.w8 = None                     # 8-bit decode mode: per layer {"qkv" | "o" | "gu" | "down": (codes, scale)}, or None (off): quantize_decode_weights / drop_decode_weights_w8
-        self.w8_epoch = None               # ops.PARAM_EPOCH the copies were quantised at
-        self.w4 = None                     # 4-bit decode mode: per layer {"qkv" | "o" | "gu" | "down": (codes, absmax)}, or None (off): quantize_decode_weights_nf4 / drop_decode_weights_w4; never set together with w8
-        self.w4_epoch = None               # ops.PARAM_EPOCH the NF4 copies were quantised at
+        self.decode_weights = None         # quantised decode mode: DecodeWeights(mode of DECODE_MODES, per layer {"qkv" | "o" | "gu" | "down": (codes, scales)}, ops.PARAM_EPOCH they were quantised at), or None (off): quantize_decode_weights / drop_decode_weights
         # RoPE in the qkv GEMM's epilogue (mp_gemm_qkv_rope_bf16) wants the q / k head rows interleaved in blocks of 32; the plain
         # fused qkv weight stays (decode GEMVs, the LoRA path's dgrad transposes, export), the interleaved copy (+3.2 GB of 288 at
         # 7B) serves every multi-row forward.  Rebuilt whenever the qkv weights change (refresh_fused_qkv).
@@ -112,75 +122,50 @@ class LlamaStack:
                 lw["qkv_rope_f"] = (lw["qkv_rope"].float() * lw["ln1"][None, :]).to(torch.bfloat16)
                 lw["gu_f"] = (lw["gu"].float() * lw["ln2"][None, None, :]).to(torch.bfloat16)
 
-    W8_KEYS = ("qkv", "o", "gu", "down")
+    DECODE_WEIGHT_KEYS = ("qkv", "o", "gu", "down")
 
-    def _decode_copies_unsupported(self, bits, multiple, why_multiple):
-        """Why this stack cannot decode from `bits`-bit copies (a sentence), or None: one list for both modes."""
-        cfg = self.cfg
+    def decode_weights_unsupported(self, bits):
+        """Why this stack cannot decode from the copies of mode DECODE_MODES[bits] (a sentence), or None: one list for every mode."""
+        cfg, mode = self.cfg, DECODE_MODES[bits]
         if any(i in self.moe_layers for i in range(len(self.layers))) and cfg.top_k_experts != 1:
-            return f"top-2 expert routing has no {bits}-bit expert GEMVs (top_k_experts == 1 only)"
+            return f"top-2 expert routing has no {mode.words} expert GEMVs (top_k_experts == 1 only)"
         if cfg.use_residual:
             return "the residual MoE (use_residual) decodes through the GEMM path, which reads the bf16 weights"
         if self.ep is not None:
-            return f"expert parallelism keeps the experts sharded; the {bits}-bit expert GEMVs run on one rank"
+            return f"expert parallelism keeps the experts sharded; the {mode.words} expert GEMVs run on one rank"
         if self.lora is not None:
-            return f"attached adapters rewrite the bf16 weights under the {bits}-bit copies (adapters_merged()): call merge_and_unload() first"
-        if cfg.hidden_size % multiple or cfg.intermediate_size % multiple:
-            return f"hidden_size={cfg.hidden_size} and intermediate_size={cfg.intermediate_size} must be multiples of {multiple} ({why_multiple})"
+            return f"attached adapters rewrite the bf16 weights under the {mode.words} copies (adapters_merged()): call merge_and_unload() first"
+        if cfg.hidden_size % mode.multiple or cfg.intermediate_size % mode.multiple:
+            return f"hidden_size={cfg.hidden_size} and intermediate_size={cfg.intermediate_size} must be multiples of {mode.multiple} ({mode.why})"
         return None
 
-    def decode_w8_unsupported(self):
-        """Why this stack cannot decode from 8-bit copies (a sentence), or None."""
-        return self._decode_copies_unsupported(8, 16, "16 codes per 16-byte load")
-
-    def decode_w4_unsupported(self):
-        """Why this stack cannot decode from NF4 copies (a sentence), or None."""
-        return self._decode_copies_unsupported(4, 64, "one absmax per block of 64 weights")
-
-    def quantize_decode_weights(self):
-        """8-bit decode mode on: row-wise absmax int8 copies (ops.quantize_rows_w8, bitsandbytes' weight format) of every layer's qkv, o, gate|up
-        and down projections, dense [N, K] and expert [E, N, K] alike (+ half the decoder's bf16 bytes; the bf16 weights stay and serve prefill,
-        training, export and the adapter merge).  While self.w8 is set, every decode row (decode_step, forward with a KV cache at pos0 > 0)
-        streams the copies.  lm_head, embed_tokens, the norms and the gate wg are not quantised.  Stamped with ops.PARAM_EPOCH: whoever decodes
-        re-quantises when the parameters were written since.  NotImplementedError (and nothing changed) where the mode is not built."""
-        why = self.decode_w8_unsupported()
+    def quantize_decode_weights(self, bits):
+        """Quantised decode mode DECODE_MODES[bits] on: copies (the mode's ops quantiser) of every layer's qkv, o, gate|up and down projections,
+        dense [N, K] and expert [E, N, K] alike, beside the bf16 weights, which stay and serve prefill, training, export and the adapter merge.
+        While self.decode_weights is set, every decode row (decode_step, forward with a KV cache at pos0 > 0) streams the copies.  lm_head,
+        embed_tokens, the norms and the gate wg are not quantised.  Stamped with ops.PARAM_EPOCH: whoever decodes re-quantises when the
+        parameters were written since.  NotImplementedError (and nothing changed, the other mode's copies included) where the mode is not built."""
+        mode = DECODE_MODES[bits]
+        why = self.decode_weights_unsupported(bits)
         if why is not None:
-            raise NotImplementedError(f"8-bit decode weights: {why}")
-        self.drop_decode_weights_w4()      # the two modes are exclusive
-        self.w8 = [{k: ops.quantize_rows_w8(lw[k]) for k in self.W8_KEYS} for lw in self.layers]
-        self.w8_epoch = ops.PARAM_EPOCH
+            raise NotImplementedError(f"{mode.words} decode weights: {why}")
+        self.drop_decode_weights()         # whichever mode was on, before the new copies are allocated: one mode at a time, no higher memory peak
+        quantize = getattr(ops, mode.quantizer)
+        self.decode_weights = DecodeWeights(mode, [{k: quantize(lw[k]) for k in self.DECODE_WEIGHT_KEYS} for lw in self.layers], ops.PARAM_EPOCH)
 
-    def drop_decode_weights_w8(self):
-        """8-bit decode mode off: the copies are dropped and every decode row reads the bf16 weights again."""
-        self.w8 = self.w8_epoch = None
-
-    def quantize_decode_weights_nf4(self):
-        """4-bit decode mode on: NF4 copies (ops.quantize_blocks_nf4: 4-bit codes, one fp32 absmax per 64 weights) of the projections the 8-bit
-        mode copies, beside the bf16 weights (+ 0.28 of the decoder's bf16 bytes); the 8-bit copies, if any, are dropped.  While self.w4 is set,
-        every decode row streams them.  Stamped with ops.PARAM_EPOCH.  NotImplementedError (and nothing changed) where the mode is not built."""
-        why = self.decode_w4_unsupported()
-        if why is not None:
-            raise NotImplementedError(f"4-bit decode weights: {why}")
-        self.drop_decode_weights_w8()      # the two modes are exclusive
-        self.w4 = [{k: ops.quantize_blocks_nf4(lw[k]) for k in self.W8_KEYS} for lw in self.layers]
-        self.w4_epoch = ops.PARAM_EPOCH
-
-    def drop_decode_weights_w4(self):
-        """4-bit decode mode off: the copies are dropped and every decode row reads the bf16 weights again."""
-        self.w4 = self.w4_epoch = None
+    def drop_decode_weights(self):
+        """Quantised decode mode off: the copies are dropped and every decode row reads the bf16 weights again."""
+        self.decode_weights = None
 
     def _decode_copies(self, i):
-        """Layer i's quantised copies of whichever mode is on (8-bit or NF4), or None: what a decode row hands down to _row_proj as q8."""
-        if self.w8 is not None:
-            return self.w8[i]
-        return self.w4[i] if self.w4 is not None else None
+        """Layer i's quantised copies of the mode that is on, or None: what a decode row hands down to _row_proj as copies."""
+        return self.decode_weights.copies[i] if self.decode_weights is not None else None
 
-    def _row_proj(self, lw, key, a, q8, **kw):
-        """THE selector of a decode-row projection (at most 8 rows): the GEMV of the mode that is on — NF4 while self.w4 is set, else 8-bit —
-        on the layer's quantised copies q8 (_decode_copies(i), handed down only for a decode row), or the bf16 GEMV on lw[key]."""
-        if q8 is not None:
-            quant_gemv = ops.gemv_w4 if self.w4 is not None else ops.gemv_w8
-            return quant_gemv(a, *q8[key], **kw)
+    def _row_proj(self, lw, key, a, copies, **kw):
+        """THE selector of a decode-row projection (at most 8 rows): the GEMV of the mode that is on, on the layer's quantised copies
+        (_decode_copies(i), handed down only for a decode row), or the bf16 GEMV on lw[key]."""
+        if copies is not None:
+            return getattr(ops, self.decode_weights.mode.gemv)(a, *copies[key], **kw)
         return ops.gemv(a, lw[key], **kw)
 
     def enable_expert_parallel(self, ep):
@@ -290,19 +275,19 @@ class LlamaStack:
         """Whether T rows of a MoE layer take the per-row expert GEMVs (the decode rows): one rank, at most 8 rows, no residual MoE."""
         return self.ep is None and T <= 8 and not self.cfg.use_residual
 
-    def _expert_gemvs_top1(self, lw, h, x, expert, slot, weight, q8=None, grouped=False):
+    def _expert_gemvs_top1(self, lw, h, x, expert, slot, weight, copies=None, grouped=False):
         """Decode rows, top-1: each row streams its own expert's matrices (GEMV with a device-side expert index); the combine weight, the
         capacity drop and the residual ride in the down projection's epilogue.  Behind _mlp's routing and behind decode_step's fused one.
         grouped (the ragged rows of a batch, bf16 weights): the rows that name the same expert share its weight pass (ops.gemv_grouped: the
         indexed form's bits); group_expert_gemvs = False keeps the indexed form (A/B)."""
-        if grouped and q8 is None and self.group_expert_gemvs:
+        if grouped and copies is None and self.group_expert_gemvs:
             act = ops.gemv_grouped(h, lw["gu"], expert, act=ops.ACT_SWIGLU_PAIR, row_keep=slot)
             return ops.gemv_grouped(act, lw["down"], expert, residual=x, row_scale=weight, row_keep=slot)
-        if q8 is not None:         # (the 8-bit and NF4 gate|up also skip a dropped row's weights; its act row stays unwritten and the down projection never reads it)
-            act = self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR, w_index=expert, row_keep=slot)
+        if copies is not None:         # (the quantised gate|up GEMVs also skip a dropped row's weights; its act row stays unwritten and the down projection never reads it)
+            act = self._row_proj(lw, "gu", h, copies, act=ops.ACT_SWIGLU_PAIR, w_index=expert, row_keep=slot)
         else:                      # (the bf16 kernel would skip it too, given row_keep; the recorded launch traces pin this call without it)
-            act = self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR, w_index=expert)
-        return self._row_proj(lw, "down", act, q8, residual=x, w_index=expert, row_scale=weight, row_keep=slot)
+            act = self._row_proj(lw, "gu", h, copies, act=ops.ACT_SWIGLU_PAIR, w_index=expert)
+        return self._row_proj(lw, "down", act, copies, residual=x, w_index=expert, row_scale=weight, row_keep=slot)
 
     def _expert_gemvs_top2(self, lw, h, x, expert, slot, weight):
         """Decode rows, top-2: the 2T (token, choice) entries stream their experts' matrices; the down projection adds both weighted expert
@@ -310,14 +295,14 @@ class LlamaStack:
         act = ops.gemv_top2_gate_up(h, lw["gu"], expert, slot)
         return ops.gemv_top2_down(act, lw["down"], expert, slot, weight, x)
 
-    def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None, pass_dev=None, q8=None, cap=None):
+    def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None, pass_dev=None, copies=None, cap=None):
         """x + MLP(h): h = post-attention RMSNorm output [T,d], x = residual stream [T,d]; gate = (logits, gates) when the caller's fused
         norm kernel already produced them (ops.rmsnorm_gate); needed = (rows, mask) when only those output rows are read (the last layer);
-        rstd: the folded post-attention norm (h is None then); q8: the layer's 8-bit or NF4 copies when the rows are decode rows; cap: the ragged rows of a batch (decode_step with `rows`) — that capacity (T: nothing dropped), no draws, the grouped expert GEMVs.  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
+        rstd: the folded post-attention norm (h is None then); copies: the layer's quantised copies (_decode_copies) when the rows are decode rows; cap: the ragged rows of a batch (decode_step with `rows`) — that capacity (T: nothing dropped), no draws, the grouped expert GEMVs.  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
         cfg, T = self.cfg, x.shape[0]
         if i not in self.moe_layers:
             if T <= 8:
-                return self._row_proj(lw, "down", self._row_proj(lw, "gu", h, q8, act=ops.ACT_SWIGLU_PAIR), q8, residual=x), None, None
+                return self._row_proj(lw, "down", self._row_proj(lw, "gu", h, copies, act=ops.ACT_SWIGLU_PAIR), copies, residual=x), None, None
             act = ops.gemm(h, lw["gu"], act=ops.ACT_SWIGLU_PAIR)       # silu(gate)*up fused into the GEMM epilogue
             return ops.gemm(act, lw["down"], residual=x), None, None
         ragged = cap is not None
@@ -327,7 +312,7 @@ class LlamaStack:
             # (no gate draws: random token selection only acts when an expert is over capacity; below cap >= T the draws are generated as usual)
             draws = None if cap >= T else self._gate_draws(i, T, E, False, pass_dev)
             expert, slot, weight, kept, counts, l_aux = ops.moe_route_top1(gates, cap, draws)
-            return self._expert_gemvs_top1(lw, h, x, expert, slot, weight, q8, grouped=ragged), l_aux, (expert, slot, counts)
+            return self._expert_gemvs_top1(lw, h, x, expert, slot, weight, copies, grouped=ragged), l_aux, (expert, slot, counts)
         if k == 2 and self._expert_gemv_rows(T):
             expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2(gates, logits, cap, self._gate_draws(i, T, E, True, pass_dev))
             return self._expert_gemvs_top2(lw, h, x, expert, slot, weight), l_aux, (expert, slot, counts)
@@ -438,12 +423,12 @@ class LlamaStack:
                 "v": [torch.empty(shape, dtype=torch.bfloat16, device=self.device) for _ in self.layers],
                 "err": torch.zeros(1, dtype=torch.int32, device=self.device)}
 
-    def _lin(self, lw, key, a, q8=None, **kw):
+    def _lin(self, lw, key, a, copies=None, **kw):
         """The projection lw[key] of a [T, K]: a handful of rows (the single-token decode steps) are a weight stream -> GEMV kernel (HBM-bound,
         _row_proj), else GEMM."""
-        return self._row_proj(lw, key, a, q8, **kw) if a.shape[0] <= 8 else ops.gemm(a, lw[key], **kw)
+        return self._row_proj(lw, key, a, copies, **kw) if a.shape[0] <= 8 else ops.gemm(a, lw[key], **kw)
 
-    def _qkv(self, lw, x, S, pos0, folded, q8=None):
+    def _qkv(self, lw, x, S, pos0, folded, copies=None):
         """input_layernorm + fused qkv projection + RoPE of the rows x [B*S, d] at positions pos0 .. pos0 + S - 1 -> qkv [B*S, 3d]."""
         cfg = self.cfg
         H, D, (T, d) = cfg.num_attention_heads, cfg.head_dim, x.shape
@@ -453,7 +438,7 @@ class LlamaStack:
         h = ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps)
         if self.fuse_rope and T > 8:       # RoPE in the epilogue (row stride of the qkv buffer kept off multiples of 8 KiB: ops.padded_rows)
             return ops.gemm_qkv_rope(h, lw["qkv_rope"], self.cos, self.sin, S, H, D, pos_offset=pos0, out=ops.padded_rows(T, 3 * d, x.device))
-        qkv = self._lin(lw, "qkv", h, q8)
+        qkv = self._lin(lw, "qkv", h, copies)
         ops.rope_qk_(qkv, self.cos, self.sin, S, H, D, pos_offset=pos0)
         return qkv
 
@@ -491,12 +476,12 @@ class LlamaStack:
             and d in ops.RMSNORM_GATE_DIMS and ops.gemm_fold_ok(B * S, 3 * d, d) and ops.gemm_fold_ok(self.capacity(B * S), 2 * cfg.intermediate_size, d)
         self.folded_layers = 0
         last = len(self.layers) - 1
-        # 8-bit / 4-bit decode mode: only a decode row (a cached step behind the prefill) streams the copies, never a short prefill or a cache-free pass
-        w8_row = (self.w8 is not None or self.w4 is not None) and kv_cache is not None and pos0 > 0 and B * S <= 8
+        # quantised decode mode: only a decode row (a cached step behind the prefill) streams the copies, never a short prefill or a cache-free pass
+        quant_row = self.decode_weights is not None and kv_cache is not None and pos0 > 0 and B * S <= 8
         for i, lw in enumerate(self.layers):
             folded = fold and "qkv_rope_f" in lw
-            q8 = self._decode_copies(i) if w8_row else None
-            q5 = self._qkv(lw, x, S, pos0, folded, q8).unflatten(0, (B, S)).unflatten(2, (3, H, D))
+            copies = self._decode_copies(i) if quant_row else None
+            q5 = self._qkv(lw, x, S, pos0, folded, copies).unflatten(0, (B, S)).unflatten(2, (3, H, D))
             if kv_cache is not None:
                 kv_cache["k"][i][:, pos0:pos0 + S].copy_(q5[:, :, 1])
                 kv_cache["v"][i][:, pos0:pos0 + S].copy_(q5[:, :, 2])
@@ -505,13 +490,13 @@ class LlamaStack:
                 attn = ops.attention(q5[:, :, 0], kv_cache["k"][i][:, :pos0 + 1], kv_cache["v"][i][:, :pos0 + 1], causal=False)
             else:
                 attn = ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], causal=True, key_valid=key_valid)
-            x = self._lin(lw, "o", attn.view(B * S, d), q8, residual=x)
+            x = self._lin(lw, "o", attn.view(B * S, d), copies, residual=x)
             # (tests / parity only: the layer's own gate input, copied before the combine writes the MLP output into the residual stream — the
             #  layer-local routing check of oracle/parity.py recomputes the gate from it)
             x_gate_in = x.clone() if (collect_routing and i in self.moe_layers) else None
             h, gate, rstd = self._post_attention_norm(i, lw, x, folded)
             # (the last layer's row set goes to _mlp whatever produced the gate: only the top-1 gather / scatter branch prunes, a dense layer ignores it)
-            x, l_aux, r = self._mlp(i, lw, h, x, gate=gate, needed=needed if i == last else None, rstd=rstd, q8=q8)
+            x, l_aux, r = self._mlp(i, lw, h, x, gate=gate, needed=needed if i == last else None, rstd=rstd, copies=copies)
             if l_aux is not None:
                 aux.append(l_aux)
                 if collect_routing:
@@ -546,7 +531,7 @@ class LlamaStack:
         of generate_batch as the rows of one step.  The layer body then takes the unfused qkv branch (the norm-folded launches have no per-row
         twin), ops.decode_rope_append_rows and ops.attention_decode_rows, and routes a MoE layer's rows with a capacity of B and no draws (no
         row is dropped because of its batch-mates: a row's answer does not depend on the others); a top-1 layer's rows share one weight pass
-        per expert (ops.gemv_grouped; the 8-bit and NF4 copies keep the indexed form).  NotImplementedError before any state changes where
+        per expert (ops.gemv_grouped; the quantised copies keep the indexed form).  NotImplementedError before any state changes where
         batch_rows_unsupported() says so.
         Reproducibility note (round-4 advisor): the narrow projections (o_proj, down) take the K-split GEMV when B == 1 or an expert index is
         given and the shared-weight form otherwise; the two add their partial dot products in different orders, so the SAME prompt decoded at
@@ -566,16 +551,16 @@ class LlamaStack:
         H, D, E, k = cfg.num_attention_heads, cfg.head_dim, cfg.num_experts, cfg.top_k_experts
         x = emb.reshape(B, d)
         self.gate_pass += 1
-        # input_layernorm inside the qkv GEMV (same bits, one launch less per layer); the norm-folded launches have no 8-bit or NF4 twins and no
+        # input_layernorm inside the qkv GEMV (same bits, one launch less per layer); the norm-folded launches have no quantised twins and no
         # per-row twin: those modes take the unfused branches
-        fold = not ragged and self.w8 is None and self.w4 is None and ops.gemv_rmsnorm_ok(B, d, head_dim=D, swiglu_n=2 * cfg.intermediate_size)
+        fold = not ragged and self.decode_weights is None and ops.gemv_rmsnorm_ok(B, d, head_dim=D, swiglu_n=2 * cfg.intermediate_size)
         for i, lw in enumerate(self.layers):
-            q8 = self._decode_copies(i)
+            copies = self._decode_copies(i)
             if fold:                                            # norm + projection + RoPE + cache append: one launch, the three launches' bits
                 qkv = ops.gemv_rmsnorm_rope_append(x, lw["ln1"], cfg.rms_norm_eps, lw["qkv"], self.cos, self.sin, kv_cache["k"][i],
                                                    kv_cache["v"][i], counters[0:1], H, D, err=kv_cache["err"])
             else:
-                qkv = self._row_proj(lw, "qkv", ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps), q8)
+                qkv = self._row_proj(lw, "qkv", ops.rmsnorm(x, lw["ln1"], cfg.rms_norm_eps), copies)
                 if ragged:
                     ops.decode_rope_append_rows(qkv, self.cos, self.sin, kv_cache["k"][i], kv_cache["v"][i], pos_rows, H, D, err=kv_cache["err"])
                 else:
@@ -585,14 +570,14 @@ class LlamaStack:
                 attn = ops.attention_decode_rows(q4, kv_cache["k"][i], kv_cache["v"][i], key_rows)
             else:
                 attn = ops.attention(q4, kv_cache["k"][i], kv_cache["v"][i], causal=False, sk_dev=counters[1:2])
-            x = self._row_proj(lw, "o", attn.view(B, d), q8, residual=x)
+            x = self._row_proj(lw, "o", attn.view(B, d), copies, residual=x)
             # post-attention norm + gate + routing in ONE launch, then the expert GEMVs of _mlp's decode-row branches (the separate kernels' bits)
             if i in self.moe_layers and self.fuse_decode_routing and self._expert_gemv_rows(B) and k in (1, 2):
                 cap = B if ragged else self.capacity(B)         # (ragged rows: generate()'s routing of each row, where nothing can be dropped)
                 if k == 1:
                     draws = None if cap >= B else self._gate_draws(i, B, E, False, pass_dev)
                     h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
-                    x = self._expert_gemvs_top1(lw, h, x, expert, slot, weight, q8, grouped=ragged)
+                    x = self._expert_gemvs_top1(lw, h, x, expert, slot, weight, copies, grouped=ragged)
                 else:
                     draws = self._gate_draws(i, B, E, True, pass_dev)
                     h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route_top2(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
@@ -602,7 +587,7 @@ class LlamaStack:
                 act = ops.gemv_rmsnorm(x, lw["ln2"], cfg.rms_norm_eps, lw["gu"], act=ops.ACT_SWIGLU_PAIR)
                 x = ops.gemv(act, lw["down"], residual=x)
             else:
-                x, _, _ = self._mlp(i, lw, ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps), x, pass_dev=pass_dev, q8=q8, cap=B if ragged else None)
+                x, _, _ = self._mlp(i, lw, ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps), x, pass_dev=pass_dev, copies=copies, cap=B if ragged else None)
         return ops.rmsnorm(x, self.norm_w, cfg.rms_norm_eps).view(B, 1, d)
 
     def next_token_logits(self, hidden_row):

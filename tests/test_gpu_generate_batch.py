@@ -1,7 +1,7 @@
 """generate_batch(): ragged prompts as the rows of one decode step, on the tiny config (dense, E = 2 top-1, E = 2 top-2).  A row of a batch is
 the single-prompt model in another summation order, so rows are compared with generate() through teacher-forced hidden states and the
 project's bound for that; no test compares TOKENS of the batch and the single-prompt path on random tiny weights (the docstring of
-tests/test_gpu_w8_decode.py says why).  What must be exact — the order of the rows, graph against loop, the output layout — is."""
+tests/test_gpu_quant_decode.py says why).  What must be exact — the order of the rows, graph against loop, the output layout — is."""
 import json
 import statistics
 
@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 KINDS = ("dense", "top1", "top2")
 N_NEW = 16
-BOUND = 2.0 ** -5            # "same function, another summation order" (BOUND of tests/test_gpu_w8_decode.py)
+BOUND = 2.0 ** -5            # "same function, another summation order" (BOUND of tests/test_gpu_quant_decode.py)
 LENGTHS = (24, 31, 17)
 EOS = 2
 
@@ -53,7 +53,7 @@ def _padded(prompts):
 
 
 class _ScriptedRows:
-    """Teacher forcing of a batch: token `step` of row b is script[b, step] (tests/test_gpu_w8_decode.py's _ScriptedPick over [B, n])."""
+    """Teacher forcing of a batch: token `step` of row b is script[b, step] (tests/test_gpu_quant_decode.py's _ScriptedPick over [B, n])."""
     needs_step = True
 
     def __init__(self, script, dev):

@@ -1,251 +1,20 @@
-"""8-bit decode weights through the model (MedPLIBForCausalLM.enable_decode_8bit, the worker's --load-8bit) on the tiny config, dense and
-E = 2 top-1: with the decoder weights snapped to the quantiser's grid the 8-bit model is the SAME function as the bf16 one (other summation
-order, unfused norms), so teacher-forced hidden states must agree within the project's bound for that; with random weights it is a different
-function, namely the bf16 model on the dequantised weights.  No test here compares TOKENS of the 8-bit and the bf16 model on random tiny
-weights: the top-2 logit gaps of such runs are 0.002-0.05, so a near-tie hatch would swallow every step."""
+"""What is 8-bit by name among the model tests of the quantised decode modes: the worker's --load-8bit, and the entry-point test of the 8-bit
+mode under the name it has always had.  Helpers, the shared body and every other test: tests/test_gpu_quant_decode.py."""
 import json
 
 import numpy as np
 import pytest
 import torch
 
-from medplib_amd import ops
-from medplib_amd.model import generation as G
-from medplib_amd.model.config import MedPLIBConfig
-from oracle import model as OM
+from test_gpu_quant_decode import KINDS, _tiny, every_decoding_entry_point_runs
 from toy_tokenizer import ToyTokenizer  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-KINDS = ("dense", "top1")
-N_NEW = 16
-BOUND = 2.0 ** -5            # "same function, another summation order" (test_decode_is_prefix_consistent_and_equals_the_prefill_at_true_dims)
-W8_KEYS = ("qkv", "o", "gu", "down")
-
-
-def _tiny(dev, kind, **kw):
-    from medplib_amd.model.medplib import LISAForCausalLM, MedPLIBForCausalLM
-    if kind == "dense":
-        cfg, cls = MedPLIBConfig.tiny(moe_enable=False, sam_depth=2, **kw), LISAForCausalLM
-    else:
-        cfg, cls = MedPLIBConfig.tiny(moe_enable=True, sam_depth=2, num_experts=2, top_k_experts=1 if kind == "top1" else 2, **kw), MedPLIBForCausalLM
-    W = OM.init_hf_weights(cfg, seed=3)
-    m = cls(cfg, device=dev)
-    m.load_hf_state_dict(W)
-    return cfg, m.eval()
-
-
-def _inputs(cfg, dev, seed=0):
-    b = OM.make_batch(cfg, 1, seed=seed)
-    return b, b["images_clip"].to(torch.bfloat16).to(dev), b["images"].to(torch.bfloat16).float().to(dev)
-
-
-class _ScriptedPick:
-    """Teacher forcing: token `step` of the answer is script[step], whatever the logits say.  needs_step: the captured step keeps the token
-    number on the device and hands it over as an int32 [1] tensor, the loop hands over an int."""
-    needs_step = True
-
-    def __init__(self, script, dev):
-        self.script = torch.as_tensor(script, dtype=torch.int64).to(dev)
-
-    def __call__(self, logits, step):
-        if torch.is_tensor(step):
-            return self.script.index_select(0, step)
-        return self.script[int(step):int(step) + 1].clone()
-
-
-def _run(m, b, clip, graph, pick=G._argmax_pick, n_new=N_NEW):
-    """One decode of n_new tokens -> (ids, [hidden [d] of every fed token] on the host); asserts the path taken."""
-    m.decode_with_graph = graph
-    with m._decoding("test"):
-        for generated, _, hiddens in m._decode(np.asarray(b["input_ids"]).astype(np.int64), clip, n_new, (), pick=pick):
-            pass
-    torch.cuda.synchronize()
-    assert m.last_decode_path == ("graph" if graph else "loop")
-    assert len(generated) == n_new and len(hiddens) == n_new
-    return list(generated), [h.reshape(-1).float().cpu() for h in hiddens[1:]]
-
-
-def _snap_to_grid(m):
-    """Every decoder projection row -> c * 2^e with integer |c| <= 127 and the row's largest entry at +-127: what the quantiser reproduces
-    exactly (tests/test_gpu_w8_gemv.py), so code * scale IS the bf16 weight."""
-    llm = m.model.llm
-    for lw in llm.layers:
-        for k in W8_KEYS:
-            w = lw[k].float()
-            absmax = w.abs().amax(-1, keepdim=True).clamp_min(2.0 ** -20)
-            step = torch.exp2(torch.ceil(torch.log2(absmax / 127.0)))
-            c = torch.round(w / step).clamp_(-127, 127)
-            at = w.abs().argmax(-1, keepdim=True)
-            c.scatter_(-1, at, 127.0 * torch.sign(w.gather(-1, at)))
-            lw[k].copy_((c * step).to(torch.bfloat16))
-            assert torch.equal(lw[k].float(), c * step)
-    llm.refresh_fused_qkv()
-    ops.PARAM_EPOCH += 1
-
-
-def _count_w8_calls(monkeypatch):
-    n = [0]
-    orig = ops.gemv_w8
-
-    def counted(*a, **kw):
-        n[0] += 1
-        return orig(*a, **kw)
-    monkeypatch.setattr(ops, "gemv_w8", counted)
-    return n
-
-
-@pytest.mark.parametrize("kind", KINDS)
-def test_teacher_forced_hidden_states_match_bf16_on_grid_weights(dev, kind, monkeypatch):
-    """The tokens of a 16-token bf16 greedy run, fed to the 8-bit run through a scripted pick: every per-step hidden state within
-    2^-5 * max|entry| of the bf16 run's, in the captured step and in the loop.  Top-1: a near-tied gate may send one step to the other
-    expert, so the bound may fail on at most one of the 15 compared steps; dense: on none."""
-    cfg, m = _tiny(dev, kind)
-    _snap_to_grid(m)
-    b, clip, _ = _inputs(cfg, dev)
-    calls = _count_w8_calls(monkeypatch)
-    for graph in (True, False):
-        m.enable_decode_8bit(False)
-        toks, hb = _run(m, b, clip, graph)
-        assert calls[0] == 0 and not m.decode_8bit
-        pick = _ScriptedPick(toks, dev)
-        toks_b, hb2 = _run(m, b, clip, graph, pick=pick)                 # (the scripted pick itself: the bf16 run again, bit for bit)
-        assert toks_b == toks and all(torch.equal(x, y) for x, y in zip(hb, hb2))
-        m.enable_decode_8bit(True)
-        toks8, h8 = _run(m, b, clip, graph, pick=pick)
-        assert m.decode_8bit and calls[0] > 0 and toks8 == toks and len(h8) == N_NEW - 1
-        rel = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(h8, hb)]
-        print(kind, "graph" if graph else "loop", "max |h8 - hbf16| / max|hbf16| per step:", " ".join(f"{r:.4f}" for r in rel))
-        assert sum(r > BOUND for r in rel) <= (1 if kind == "top1" else 0), rel
-        calls[0] = 0
-
-
-@pytest.mark.parametrize("kind", KINDS)
-def test_mode_is_really_on_with_random_weights(dev, kind):
-    """Off-grid weights: the 8-bit run's first decode-step hidden state differs from the bf16 run's, and equals — within the same bound — a
-    bf16 run on a model whose decoder projections were replaced by bf16(code * scale).  That second comparison carries one extra bf16
-    rounding of the weights (code * scale has up to 7 + 24 significant bits), and the 8-bit run's PREFILL used the original bf16 weights where
-    the other model's used the dequantised ones; both are far below the bound."""
-    cfg, m = _tiny(dev, kind)
-    b, clip, _ = _inputs(cfg, dev)
-    toks, _ = _run(m, b, clip, True, n_new=4)
-    pick = _ScriptedPick(toks, dev)
-    _, hb = _run(m, b, clip, True, pick=pick, n_new=4)
-    m.enable_decode_8bit(True)
-    _, h8 = _run(m, b, clip, True, pick=pick, n_new=4)
-    assert not torch.equal(h8[0], hb[0])
-    m.enable_decode_8bit(False)
-    llm = m.model.llm
-    for lw in llm.layers:
-        for k in W8_KEYS:
-            codes, scale = ops.quantize_rows_w8(lw[k])
-            lw[k].copy_((codes.float() * scale.unsqueeze(-1)).to(torch.bfloat16))
-    llm.refresh_fused_qkv()
-    ops.PARAM_EPOCH += 1
-    _, hq = _run(m, b, clip, True, pick=pick, n_new=4)
-    rel_q = float((h8[0] - hq[0]).abs().max() / hq[0].abs().max())
-    rel_b = float((h8[0] - hb[0]).abs().max() / hb[0].abs().max())
-    print(kind, f"step 1: |h8 - h(dequantised bf16)| = {rel_q:.5f}, |h8 - h(bf16)| = {rel_b:.5f} (of the max entry)")
-    assert rel_q <= BOUND
-
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_every_decoding_entry_point_runs_in_8bit_mode(dev, kind, monkeypatch):
-    cfg, m = _tiny(dev, kind)
-    b, clip, sam = _inputs(cfg, dev)
-    n_in = b["input_ids"].shape[1]
-    m.enable_decode_8bit(True)
-    calls = _count_w8_calls(monkeypatch)
-    for graph in (True, False):
-        m.decode_with_graph = graph
-        path = "graph" if graph else "loop"
-        seen = calls[0]
-        out = m.generate(b["input_ids"], images=clip, max_new_tokens=6, eos_token_id=-1)
-        assert out.shape == (1, n_in + 6) and m.last_decode_path == path and calls[0] > seen
-        seen = calls[0]
-        out = m.generate_sample(b["input_ids"], images=clip, max_new_tokens=6, eos_token_id=-1, temperature=0.8, sample_seed=5)
-        assert out.shape == (1, n_in + 6) and m.last_decode_path == path and calls[0] > seen
-        again = m.generate_sample(b["input_ids"], images=clip, max_new_tokens=6, eos_token_id=-1, temperature=0.8, sample_seed=5)
-        assert torch.equal(out, again), "one seed, one answer"
-        seen = calls[0]
-        out = m.generate_beam(b["input_ids"], images=clip, max_new_tokens=6, eos_token_id=-1, num_beams=3)      # M = 3 rows per step
-        assert out.shape == (1, n_in + 6) and m.last_decode_path == path and calls[0] > seen
-        seen = calls[0]
-        ys = list(m.generate_stream(b["input_ids"], clip, temperature=0.0, max_new_tokens=6, eos_token_id=-1))
-        assert len(ys[-1][0]) == 6 and m.last_decode_path == path and calls[0] > seen
-        greedy = m.generate(b["input_ids"], images=clip, max_new_tokens=6, eos_token_id=-1)[0, n_in:].tolist()
-        assert ys[-1][0] == greedy
-    ids, masks = m.evaluate(clip, sam, b["input_ids"], b["resize_list"], b["label_list"], max_new_tokens=6, eos_token_id=-1)
-    assert ids.shape == (1, n_in + 6) and len(masks) == 1 and masks[0].dim() == 3 and m.decode_8bit
-
-
-@pytest.mark.parametrize("kind", KINDS)
-def test_off_means_off(dev, kind):
-    cfg, m = _tiny(dev, kind)
-    b, clip, _ = _inputs(cfg, dev)
-    for graph in (True, False):
-        before = _run(m, b, clip, graph)
-        m.enable_decode_8bit(True)
-        _run(m, b, clip, graph, n_new=4)
-        m.enable_decode_8bit(False)
-        assert not m.decode_8bit and m.model.llm.w8 is None
-        after = _run(m, b, clip, graph)
-        assert after[0] == before[0] and all(torch.equal(x, y) for x, y in zip(after[1], before[1]))
-
-
-@pytest.mark.parametrize("kind", KINDS)
-def test_a_parameter_write_requantises_before_the_next_decode(dev, kind):
-    """ops.PARAM_EPOCH moves (an optimizer step, a checkpoint load): the decode prologue re-quantises, so the next decode equals that of a
-    freshly enabled model — and not the decode before the write."""
-    cfg, m = _tiny(dev, kind)
-    b, clip, _ = _inputs(cfg, dev)
-    m.enable_decode_8bit(True)
-    old = _run(m, b, clip, True)
-    for lw in m.model.llm.layers:
-        lw["o"].mul_(0.5)
-        lw["down"].mul_(-1.0)
-    ops.PARAM_EPOCH += 1
-    assert m.model.llm.w8_epoch != ops.PARAM_EPOCH
-    new = _run(m, b, clip, True)
-    assert m.model.llm.w8_epoch == ops.PARAM_EPOCH
-    m.enable_decode_8bit(False)
-    m.enable_decode_8bit(True)
-    fresh = _run(m, b, clip, True)
-    assert new[0] == fresh[0] and all(torch.equal(x, y) for x, y in zip(new[1], fresh[1]))
-    assert not all(torch.equal(x, y) for x, y in zip(new[1], old[1]))
-
-
-def test_refusals_leave_the_model_decoding_in_bf16(dev, monkeypatch):
-    from medplib_amd.model.llama import LlamaStack
-    calls = _count_w8_calls(monkeypatch)
-
-    def refused(m, cfg, match):
-        b, clip, _ = _inputs(cfg, dev)
-        before = m.generate(b["input_ids"], images=clip, max_new_tokens=4, eos_token_id=-1)
-        with pytest.raises(NotImplementedError, match=match):
-            m.enable_decode_8bit(True)
-        assert not m.decode_8bit
-        assert torch.equal(m.generate(b["input_ids"], images=clip, max_new_tokens=4, eos_token_id=-1), before) and calls[0] == 0
-
-    cfg, m = _tiny(dev, "top2")
-    refused(m, cfg, "top-2")
-    cfg, m = _tiny(dev, "top1", use_residual=True)
-    refused(m, cfg, "use_residual")
-    cfg, m = _tiny(dev, "top1")
-    m.enable_lora(lora_r=8, lora_alpha=16, lora_target_modules="gate_proj,up_proj,down_proj")
-    refused(m.eval(), cfg, "merge_and_unload")
-    # adapters attached AFTER the mode was enabled: the decode prologue refuses, before anything is decoded
-    cfg, m = _tiny(dev, "dense")
-    m.enable_decode_8bit(True)
-    m.enable_lora(lora_r=8, lora_alpha=16, lora_target_modules="gate_proj,up_proj,down_proj")
-    b, clip, _ = _inputs(cfg, dev)
-    with pytest.raises(NotImplementedError, match="merge_and_unload"):
-        m.eval().generate(b["input_ids"], images=clip, max_new_tokens=4, eos_token_id=-1)
-    # a K that is no multiple of 16 (the stack alone: no decode launch takes such a config either way)
-    llm = LlamaStack(MedPLIBConfig.tiny(moe_enable=False, intermediate_size=328), dev)
-    with pytest.raises(NotImplementedError, match="multiples of 16"):
-        llm.quantize_decode_weights()
-    assert llm.w8 is None and calls[0] == 0
+    every_decoding_entry_point_runs(dev, 8, kind, monkeypatch)
 
 
 class _Tok(ToyTokenizer):

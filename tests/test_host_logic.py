@@ -744,3 +744,85 @@ def test_check_full_size_names_every_violated_bound():
     bad(["routing", "slots_equal_deepspeed_rule_every_layer"], False)
     bad(["routing", "kept_state_differs_on_agreeing_rows_per_layer"], [7, 0, 1, 0])
     assert len(check_full_size(dict(good, routing_agreement_per_layer=[0.99] * 3), 4, True)) == 1
+
+
+# ---------------------------------------------------------------- quantised decode weights: the state machine of LlamaStack on a stub stack
+def _stub_stack(monkeypatch, intermediate_size=176):
+    """A LlamaStack of one dense layer of small CPU tensors, built without __init__, and the two ops quantisers replaced by recording fakes:
+    log gets (quantiser name, the stack's decode_weights at the call) per call, and a fake returns (name, the weight) as the copy."""
+    import types
+    from medplib_amd import ops
+    from medplib_amd.model.llama import LlamaStack
+    s = LlamaStack.__new__(LlamaStack)
+    s.cfg = types.SimpleNamespace(hidden_size=64, intermediate_size=intermediate_size, top_k_experts=1, use_residual=False)
+    s.layers = [{k: torch.zeros(2, 2) for k in LlamaStack.DECODE_WEIGHT_KEYS}]
+    s.moe_layers, s.ep, s.lora, s.decode_weights = set(), None, None, None
+    log = []
+    for name in ("quantize_rows_w8", "quantize_blocks_nf4"):
+        monkeypatch.setattr(ops, name, lambda w, name=name: (log.append((name, s.decode_weights)), (name, w))[1])
+    return s, log, ops
+
+
+def test_a_refused_switch_of_decode_mode_changes_nothing_and_quantises_nothing(monkeypatch):
+    s, log, ops = _stub_stack(monkeypatch)              # 176: a multiple of 16, not of 64
+    s.quantize_decode_weights(8)
+    held, copies = s.decode_weights, s.decode_weights.copies
+    assert held.mode.bits == 8 and [n for n, _ in log] == ["quantize_rows_w8"] * 4
+    del log[:]
+    monkeypatch.setattr(ops, "PARAM_EPOCH", ops.PARAM_EPOCH + 1)        # (a stamp by the refused call would show)
+    with pytest.raises(NotImplementedError, match="^4-bit decode weights: .*multiples of 64"):
+        s.quantize_decode_weights(4)
+    assert s.decode_weights is held and held.copies is copies and held.epoch == ops.PARAM_EPOCH - 1 and log == []
+
+
+def test_an_accepted_switch_drops_the_old_copies_before_the_new_quantiser_runs(monkeypatch):
+    s, log, _ = _stub_stack(monkeypatch, intermediate_size=192)
+    s.quantize_decode_weights(8)
+    assert [seen for _, seen in log] == [None] * 4      # (from off: nothing to drop)
+    del log[:]
+    s.quantize_decode_weights(4)
+    assert log == [("quantize_blocks_nf4", None)] * 4, "the 8-bit copies were still held while NF4 copies were made"
+    assert s.decode_weights.mode.bits == 4 and len(s.decode_weights.copies) == 1
+    assert {k: c[0] for k, c in s.decode_weights.copies[0].items()} == dict.fromkeys(s.DECODE_WEIGHT_KEYS, "quantize_blocks_nf4")
+    assert all(c[1] is s.layers[0][k] for k, c in s.decode_weights.copies[0].items())
+    del log[:]
+    s.quantize_decode_weights(4)                        # the mode that is on, again: re-quantised, the stale copies dropped first as well
+    assert log == [("quantize_blocks_nf4", None)] * 4
+
+
+def test_drop_decode_weights_with_nothing_on_is_a_no_op_and_the_epoch_is_that_of_the_call(monkeypatch):
+    s, log, ops = _stub_stack(monkeypatch)
+    s.drop_decode_weights()
+    assert s.decode_weights is None and log == []
+    monkeypatch.setattr(ops, "PARAM_EPOCH", ops.PARAM_EPOCH + 41)
+    s.quantize_decode_weights(8)
+    assert s.decode_weights.epoch == ops.PARAM_EPOCH
+    monkeypatch.setattr(ops, "PARAM_EPOCH", ops.PARAM_EPOCH + 1)
+    assert s.decode_weights.epoch == ops.PARAM_EPOCH - 1
+    s.drop_decode_weights()
+    s.drop_decode_weights()
+    assert s.decode_weights is None
+
+
+@pytest.mark.parametrize("bits, multiple, why", [(8, 16, "16 codes per 16-byte load"), (4, 64, "one absmax per block of 64 weights")])
+def test_decode_weights_unsupported_says_the_five_sentences(monkeypatch, bits, multiple, why):
+    s, log, _ = _stub_stack(monkeypatch, intermediate_size=192)
+    assert s.decode_weights_unsupported(bits) is None
+    s.moe_layers, s.cfg.top_k_experts = {0}, 2
+    assert s.decode_weights_unsupported(bits) == f"top-2 expert routing has no {bits}-bit expert GEMVs (top_k_experts == 1 only)"
+    s.cfg.top_k_experts = 1
+    assert s.decode_weights_unsupported(bits) is None, "a top-1 MoE layer is served"
+    s.cfg.use_residual = True
+    assert s.decode_weights_unsupported(bits) == "the residual MoE (use_residual) decodes through the GEMM path, which reads the bf16 weights"
+    s.cfg.use_residual, s.ep = False, object()
+    assert s.decode_weights_unsupported(bits) == f"expert parallelism keeps the experts sharded; the {bits}-bit expert GEMVs run on one rank"
+    s.ep, s.lora = None, object()
+    assert s.decode_weights_unsupported(bits) == f"attached adapters rewrite the bf16 weights under the {bits}-bit copies (adapters_merged()): call merge_and_unload() first"
+    s.lora = None
+    for d, ff in ((64 + multiple // 2, 192), (64, 192 + multiple // 2)):
+        s.cfg.hidden_size, s.cfg.intermediate_size = d, ff
+        assert s.decode_weights_unsupported(bits) == f"hidden_size={d} and intermediate_size={ff} must be multiples of {multiple} ({why})"
+    with pytest.raises(NotImplementedError) as e:
+        s.quantize_decode_weights(bits)
+    assert str(e.value) == f"{bits}-bit decode weights: hidden_size=64 and intermediate_size={192 + multiple // 2} must be multiples of {multiple} ({why})"
+    assert s.decode_weights is None and log == []

@@ -76,7 +76,7 @@ def test_model_api_has_the_4bit_pair_and_the_worker_points_to_it():
     from medplib_amd.model.llama import LlamaStack
     from model.serve import model_worker as MW
     assert isinstance(GenerationMixin.decode_4bit, property) and callable(GenerationMixin.enable_decode_4bit)
-    for name in ("quantize_decode_weights_nf4", "drop_decode_weights_w4", "decode_w4_unsupported"):
+    for name in ("quantize_decode_weights", "drop_decode_weights", "decode_weights_unsupported"):
         assert callable(getattr(LlamaStack, name))
     with pytest.raises(ValueError, match="enable_decode_4bit") as e:
         MW.check_placement(MW.parse_args(["--model-path", "checkpoints/tiny", "--device_map", "cuda", "--load-4bit"]))
