@@ -155,6 +155,23 @@ int mp_quantize_blocks_nf4_bf16(const void* W, int64_t ldw, int64_t rows, int K,
 int mp_gemv_w4_bf16(const void* x, int64_t ldx, const void* codes, int64_t ldw_bytes, int64_t strideW_bytes, const float* absmax, int64_t lda,
                     int64_t strideA, void* y, int64_t ldy, const float* bias, const void* residual, int64_t ldr, const int* w_index,
                     const float* row_scale, const int* row_keep, int M, int N, int K, int act, int out_dtype, float alpha, hipStream_t stream);
+/* mp_gemv_grouped_bf16 on the quantised copies: the indexed (expert) forms of mp_gemv_w8_bf16 / mp_gemv_w4_bf16 with one code stream per EXPERT
+ * instead of one per row.  Arguments are mp_gemv_grouped_bf16's with the weight operands of mp_gemv_w8_bf16 (codes [E, N, K] int8, scale
+ * [E, N] at strideScale) / of mp_gemv_w4_bf16 (codes [E, N, K / 2] with byte strides, absmax [E, N, K / 64] at lda, strideA).  Semantics are
+ * mp_gemv_grouped_bf16's: kept rows expert by expert in ascending row order, an expert nobody names and a dropped row stream nothing, a row
+ * whose w_index lies outside [0, E) reads nothing and is stored as a dropped row; bf16 output; MP_ACT_NONE or MP_ACT_SWIGLU_PAIR.
+ * Contract: row for row bit-identical with the indexed form of mp_gemv_w8_bf16 / mp_gemv_w4_bf16 given the same w_index, row_scale, row_keep
+ * and residual, whatever the other rows of the launch are (the same per-lane order, load widths — NF4: 16-byte loads in the wave form, 8-byte
+ * in the K-split form — wave reduction, K-part order, scales and epilogues; the K-split form under the same predicate).  A pass holds up to
+ * four rows in the int8 wave form and up to two in the others.  1 <= M <= 8, E >= 1, K % 16 == 0 (int8) / K % 64 == 0 and
+ * mp_gemv_w4_bf16's stride rules (NF4) (MP_ERR_SHAPE); a null operand (w_index is required), another activation, SWIGLU_PAIR with
+ * N % 64 != 0 or a residual (MP_ERR_ARG). */
+int mp_gemv_grouped_w8_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, const float* scale, int64_t strideScale,
+                            void* y, int64_t ldy, const void* residual, int64_t ldr, const int* w_index, const float* row_scale,
+                            const int* row_keep, int M, int N, int K, int E, int act, hipStream_t stream);
+int mp_gemv_grouped_w4_bf16(const void* x, int64_t ldx, const void* codes, int64_t ldw_bytes, int64_t strideW_bytes, const float* absmax,
+                            int64_t lda, int64_t strideA, void* y, int64_t ldy, const void* residual, int64_t ldr, const int* w_index,
+                            const float* row_scale, const int* row_keep, int M, int N, int K, int E, int act, hipStream_t stream);
 /* Top-2 MoE decode rows (tokens <= 8), the expert GEMVs over the 2 * tokens entries of mp_moe_route_top2's layout (entry c * tokens + t =
  * choice c of token t; expert[e], slot[e] < 0 = dropped, weight[e]).  gate|up: act[e, :N/2] = SwiGLU-paired x[t] . W[expert[e]] (W [E, N, K]
  * interleaved gate|up rows; dropped entries are skipped and their rows left unwritten).  down: y[t] = residual[t] + sum over the kept choices

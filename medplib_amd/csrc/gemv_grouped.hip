@@ -1,53 +1,18 @@
-// The GROUPED expert GEMV of a decode step whose rows are the prompts of a batch (generate_batch): mp_gemv_bf16's indexed form with one weight
-// stream per EXPERT instead of one per row.  The indexed kernels of gemv_forms.h take the rows one after the other, each streaming its own
-// expert's matrix, so B rows of a top-1 layer read B matrices even when E = 2.  Here a wave sorts the kept rows by expert — lane m holds row
-// m's (w_index, row_keep), a ballot per group — and streams its four W rows of an expert ONCE against all of that expert's x rows, in passes
-// of at most four rows (the shared form's register budget).  An expert no kept row names streams nothing; a dropped row streams nothing.
-// Row for row BIT-IDENTICAL with mp_gemv_bf16 given the same arguments: a lane's share of x[m] . W[n] is summed over the same k in the same
-// ascending order (wave form: k = 8 lane + 512 s, WeightBf16::row_dot's; K-split form: k = 8 lane + 512 kp + 2048 s, part_dot's), then
-// wave_sum, then the four K parts in ascending kp (KsplitWave::sum), then the same epilogues of gemv_epilogue.h.  Only the number of x rows
-// that share a loaded W vector differs.  bf16 weights only: the int8 and NF4 copies keep the indexed form.
-#include "gemv_forms.h"
+// The GROUPED expert GEMVs of a decode step whose rows are the prompts of a batch (generate_batch): the indexed form of mp_gemv_bf16 and of
+// mp_gemv_w8_bf16 with one weight stream per EXPERT instead of one per row (the NF4 twin, mp_gemv_grouped_w4_bf16, is in gemv_w4.hip beside the
+// helpers it needs).  The indexed kernels of gemv_forms.h take the rows one after the other, each streaming its own expert's matrix, so B rows
+// of a top-1 layer read B matrices even when E = 2.  Here a wave sorts the kept rows by expert — lane m holds row m's (w_index, row_keep), a
+// ballot per group (GroupedRows, gemv_grouped.h) — and streams its four W rows of an expert ONCE against all of that expert's x rows, in passes
+// of at most four rows (the shared form's register budget; two in the sixteen-wave int8 form).  An expert no kept row names streams nothing; a
+// dropped row streams nothing.
+// Row for row BIT-IDENTICAL with the indexed form of the same weight type given the same arguments: a lane's share of x[m] . W[n] is summed
+// over the same k in the same ascending order (bf16 wave form: k = 8 lane + 512 s, WeightBf16::row_dot's; K-split form: k = 8 lane + 512 kp +
+// 2048 s, part_dot's; int8: gq_stream's one FMA per weight at k = 16 lane + 1024 s, or 16 lane + 1024 kp + 4096 s), then wave_sum, then the
+// four K parts in ascending kp (KsplitWave::sum), then the row's scale (int8) and the same epilogues of gemv_epilogue.h.  Only the number of x
+// rows that share a loaded W vector differs.  Measured: profiles/batch_decode.md.
+#include "gemv_grouped.h"
 
 namespace {
-
-struct GroupedArgs {
-  GemvArgs g;
-  int E;
-};
-
-// The rows of a launch as a wave sees them: `todo` = the kept rows still to be computed, `dead` = the rows that stream nothing (row_keep < 0, or
-// an expert index outside [0, E): such a row is stored as a dropped one instead of reading past the weight tensor).  Wave-uniform.
-struct GroupedRows {
-  int ev;                          // lane m < M: w_index[m]
-  bool live;                       // lane m: row m is kept
-  unsigned long long todo, dead;
-  __device__ __forceinline__ GroupedRows(const GroupedArgs& a, int lane) {
-    const GemvArgs& g = a.g;
-    int kv = 0;
-    ev = 0;
-    if (lane < g.M) { ev = g.w_index[lane]; kv = g.row_keep ? g.row_keep[lane] : 0; }
-    live = lane < g.M && kv >= 0 && ev >= 0 && ev < a.E;
-    todo = __ballot(live);
-    dead = __ballot(lane < g.M && !live);
-  }
-  // The next pass: the lowest row still to do and up to three more rows of its expert, ascending -> their count; sel = the rows, four bits each.
-  __device__ __forceinline__ int next(int& e, unsigned& sel) {
-    const int m0 = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
-    e = __builtin_amdgcn_readlane(ev, m0);
-    unsigned long long grp = __ballot(live && ev == e) & todo;
-    int cnt = 0;
-    sel = 0;
-    while (grp && cnt < 4) {
-      const int m = __ffsll((long long)grp) - 1;
-      sel |= (unsigned)m << (4 * cnt);
-      ++cnt;
-      grp &= grp - 1;
-      todo &= ~(1ull << m);
-    }
-    return cnt;
-  }
-};
 
 // This lane's share of x[row j] . W[row r] for the NR rows of a pass: the steps k0, k0 + kstep, ... < K in ascending order in every (j, r)
 // chain.  PAIRS: two steps per trip (8 weight loads in flight per lane, as WeightBf16::shared_dot and part_dot); without, one step per trip —
@@ -90,12 +55,6 @@ __device__ __forceinline__ void gg_dot(const bf16_t* const (&xp)[NR], const bf16
   for (int j = 0; j < NR; ++j)
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[j][r] = wave_sum(acc[j][r]);
-}
-
-template <int NR>
-__device__ __forceinline__ void gg_x_rows(const GemvArgs& g, unsigned sel, const bf16_t* (&xp)[NR]) {
-#pragma unroll
-  for (int j = 0; j < NR; ++j) xp[j] = g.x + (int64_t)((sel >> (4 * j)) & 15u) * g.ldx;
 }
 
 // ---------------- the wave-per-four-rows form (gate|up with SwiGLU; a plain projection outside the K-split shape) ----------------
@@ -190,6 +149,204 @@ __global__ __launch_bounds__(1024) void gemv_grouped_ksplit_kernel(GroupedArgs a
   }
 }
 
+// ---------------- int8 codes (the copies of enable_decode_8bit): mp_gemv_w8_bf16's indexed form, one code stream per expert ----------------
+// gq_fma16 with the four dwords of a load taken strictly one after the other (FENCED): an empty asm that names the accumulators and the next
+// dword of each code row keeps the compiler from converting all sixty-four codes of a step to fp32 ahead of the first FMA, which is what
+// costs gq_stream its ~110 VGPRs with one row.  The same FMAs in the same order in every chain.
+template <int NR>
+__device__ __forceinline__ void gq_fma16_fenced(const X16 (&x)[NR], i32x4 (&w)[4], float (&acc)[NR][4]) {
+  static_assert(NR == 2, "the fence names the accumulators of a two-row pass");
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    float c[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) c[r][b] = (float)(int8_t)(w[r][q] >> (8 * b));
+#pragma unroll
+    for (int m = 0; m < NR; ++m)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const float xf = (float)(q < 2 ? x[m].a[(q & 1) * 4 + b] : x[m].b[(q & 1) * 4 + b]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[m][r] = fmaf(c[r][b], xf, acc[m][r]);
+      }
+    if (q < 3) {
+      int n0 = w[0][q + 1], n1 = w[1][q + 1], n2 = w[2][q + 1], n3 = w[3][q + 1];
+      asm volatile("" : "+v"(n0), "+v"(n1), "+v"(n2), "+v"(n3), "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[0][3]),
+                   "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[1][2]), "+v"(acc[1][3]));
+      w[0][q + 1] = n0; w[1][q + 1] = n1; w[2][q + 1] = n2; w[3][q + 1] = n3;
+    }
+  }
+}
+
+// gq_stream (gemv_forms.h) over the rows of a pass, which are not equally spaced in memory: the same trips — one step of 4 x 16 bytes per lane
+// with the next step requested before this one is multiplied — and in every (x row, W row) chain gq_fma16's one FMA per weight in ascending
+// k, so a row's sum has the bits of the indexed form's gq_stream<1> however many rows share the loaded codes.
+// XPRE = false (the sixteen-wave form with two rows, 128 VGPRs per lane): only the codes are requested a step ahead, the x rows of a step are
+// loaded in the trip that multiplies them, after the next step's codes have been requested — they come from the cache while those are in flight.
+// With both a step ahead two rows spilled 72 bytes per lane, and 52 with FENCED alone; with both switches the kernel has 128 VGPRs and no scratch.
+template <int NR, bool XPRE = true, bool FENCED = false>
+__device__ __forceinline__ void gq_stream_rows(const bf16_t* const (&xp)[NR], const int8_t* const (&wp)[4], int k, int kstep, int K,
+                                               float (&acc)[NR][4]) {
+  if (k >= K) return;
+  i32x4 w[4];
+  X16 xs[NR];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) w[r] = gq_ldw(wp[r] + k);
+  if constexpr (XPRE) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j) xs[j] = gq_ldx(xp[j] + k);
+  }
+#pragma unroll 1
+  for (; k < K; k += kstep) {
+    i32x4 wn[4] = {w[0], w[1], w[2], w[3]};
+    X16 xn[NR];
+    if constexpr (XPRE) {
+#pragma unroll
+      for (int j = 0; j < NR; ++j) xn[j] = xs[j];
+    }
+    if (k + kstep < K) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) wn[r] = gq_ldw(wp[r] + k + kstep);
+      if constexpr (XPRE) {
+#pragma unroll
+        for (int j = 0; j < NR; ++j) xn[j] = gq_ldx(xp[j] + k + kstep);
+      }
+    }
+    if constexpr (!XPRE) {
+#pragma unroll
+      for (int j = 0; j < NR; ++j) xs[j] = gq_ldx(xp[j] + k);
+    }
+    if constexpr (FENCED) gq_fma16_fenced<NR>(xs, w, acc);
+    else gq_fma16<NR>(xs, w, acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w[r] = wn[r];
+    if constexpr (XPRE) {
+#pragma unroll
+      for (int j = 0; j < NR; ++j) xs[j] = xn[j];
+    }
+  }
+}
+
+using GroupedArgsW8 = GroupedArgsT<int8_t>;
+// Pass widths (profiles/batch_decode.md).  Wave form: four rows, 230 VGPRs and two waves per SIMD.  Passes of two (168 VGPRs, three waves) were
+// measured too: the gate|up launch alone at two rows per expert 54.0 against 58.9 us, but the 7B batch step, whose rows split 3 + 1 and 4 + 0
+// as well, 5.07 against 4.90 ms at B = 4 and 9.00 against 8.64 at B = 8 — the step decides.  K-split form (1024 threads, 128 VGPRs per lane):
+// two rows; four spilled 156 bytes per lane.
+#define MP_GQ_WAVE_PASSES MP_GG_PASSES_OF_FOUR
+#define MP_GQ_KSPLIT_PASSES MP_GG_PASSES_OF_TWO
+
+// the wave-per-four-rows form: passes of up to GQ_WAVE_ROWS rows
+template <int NR, bool SWIGLU>
+__device__ __forceinline__ void gq_wave_pass(const GemvArgsT<int8_t>& g, int e, unsigned sel, const int8_t* const (&wp)[4], const int (&rows)[4],
+                                             int lane) {
+  const bf16_t* xp[NR];
+  gg_x_rows<NR>(g, sel, xp);
+  float acc[NR][4];
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[j][r] = 0.f;
+  gq_stream_rows<NR>(xp, wp, lane * 16, 1024, g.K, acc);
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[j][r] = wave_sum(acc[j][r]);
+  if (lane != 0) return;
+  float sc[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) sc[r] = g.scale[(int64_t)e * g.strideScale + min(rows[r], g.N - 1)];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int m = (sel >> (4 * j)) & 15u;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[j][r] = sc[r] * acc[j][r];
+    if (SWIGLU) {
+      gv_swiglu_store(acc[j], rows, g.N, 1.f, reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy);
+    } else {
+      const float scale = gv_row_scale(g, m);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (rows[r] < g.N) gv_store_indexed(g, m, rows[r], acc[j][r], scale);
+    }
+  }
+}
+
+template <bool SWIGLU>
+__global__ __launch_bounds__(256) void gemv_grouped_w8_kernel(GroupedArgsW8 a) {
+  const GemvArgsT<int8_t>& g = a.g;
+  const int lane = threadIdx.x & 63;
+  const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
+  int rows[4];
+  gv_wave_rows<SWIGLU>(wid, rows);
+  if (rows[0] >= g.N) return;
+  GroupedRows gr(a, lane);
+  if (!SWIGLU && lane < 4 && wid * 4 + lane < g.N) {        // dropped rows: gv_store_dropped (the SwiGLU form leaves them unwritten)
+    for (unsigned long long d = gr.dead; d; d &= d - 1) gv_store_dropped(g, __ffsll((long long)d) - 1, wid * 4 + lane);
+  }
+  while (gr.todo) {
+    int e;
+    unsigned sel;
+    const int cnt = gr.next(e, sel);
+    const int8_t* Wm = g.W + (int64_t)e * g.strideW;
+    const int8_t* wp[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(rows[r], g.N - 1) * g.ldw;
+#define MP_GQ_PASS(NR, SEL) gq_wave_pass<NR, SWIGLU>(g, e, SEL, wp, rows, lane)
+    MP_GQ_WAVE_PASSES(cnt, sel, MP_GQ_PASS);
+#undef MP_GQ_PASS
+  }
+}
+
+// the sixteen-wave K-split form: wave (rg, kp) takes the steps kp, kp + 4, ... of 1024 elements (WeightInt8::part_dot's)
+template <int NR>
+__device__ __forceinline__ void gq_ksplit_pass(const GemvArgsT<int8_t>& g, int e, unsigned sel, const int8_t* const (&wp)[4], KsplitWave& w,
+                                               float (&red)[4][4][4]) {
+  const bf16_t* xp[NR];
+  gg_x_rows<NR>(g, sel, xp);
+  float acc[NR][4];
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[j][r] = 0.f;
+  gq_stream_rows<NR, (NR == 1), (NR > 1)>(xp, wp, w.lane * 16 + w.kp * 1024, 4096, g.K, acc);
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[j][r] = wave_sum(acc[j][r]);
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int m = (sel >> (4 * j)) & 15u;
+    float s = w.sum(red, acc[j]);                            // (every wave of the workgroup: the passes are uniform over it)
+    if (!w.fin) continue;
+    s = g.scale[(int64_t)e * g.strideScale + w.n] * s;
+    gv_store_indexed(g, m, w.n, s, gv_row_scale(g, m));
+  }
+}
+
+__global__ __launch_bounds__(1024) void gemv_grouped_w8_ksplit_kernel(GroupedArgsW8 a) {
+  __shared__ float red[4][4][4];
+  const GemvArgsT<int8_t>& g = a.g;
+  KsplitWave w(g.N);
+  GroupedRows gr(a, w.lane);
+  if (w.fin) {
+    for (unsigned long long d = gr.dead; d; d &= d - 1) gv_store_dropped(g, __ffsll((long long)d) - 1, w.n);
+  }
+  while (gr.todo) {
+    int e;
+    unsigned sel;
+    const int cnt = gr.next(e, sel);
+    const int8_t* Wm = g.W + (int64_t)e * g.strideW;
+    const int8_t* wp[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(w.row0 + r, g.N - 1) * g.ldw;
+#define MP_GQ_PASS(NR, SEL) gq_ksplit_pass<NR>(g, e, SEL, wp, w, red)
+    MP_GQ_KSPLIT_PASSES(cnt, sel, MP_GQ_PASS);
+#undef MP_GQ_PASS
+  }
+}
+
 }  // namespace
 
 extern "C" int mp_gemv_grouped_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy,
@@ -212,4 +369,27 @@ extern "C" int mp_gemv_grouped_bf16(const void* x, int64_t ldx, const void* W, i
   if (act == ACT_SWIGLU_PAIR) hipLaunchKernelGGL(gemv_grouped_kernel<true>, grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL(gemv_grouped_kernel<false>, grid, dim3(256), 0, stream, a);
   return mp_check_launch("mp_gemv_grouped_bf16");
+}
+
+extern "C" int mp_gemv_grouped_w8_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, const float* scale,
+                                       int64_t strideScale, void* y, int64_t ldy, const void* residual, int64_t ldr, const int* w_index,
+                                       const float* row_scale, const int* row_keep, int M, int N, int K, int E, int act, hipStream_t stream) {
+  MP_REQUIRE(M >= 1 && M <= GV_MAXM && N > 0 && K > 0 && K % 16 == 0 && ldx % 8 == 0 && ldw % 16 == 0 && strideW % 16 == 0 && E >= 1, MP_ERR_SHAPE,
+             "mp_gemv_grouped_w8_bf16: 1 <= M <= 8, K %% 16 == 0, E >= 1 (M=%d N=%d K=%d E=%d)", M, N, K, E);
+  MP_REQUIRE(x && W && scale && y && w_index, MP_ERR_ARG,
+             "mp_gemv_grouped_w8_bf16: null operand (the grouped form is the indexed one: w_index is required)");
+  MP_REQUIRE(act == ACT_NONE || act == ACT_SWIGLU_PAIR, MP_ERR_ARG, "mp_gemv_grouped_w8_bf16: only NONE / SWIGLU_PAIR (activation %d)", act);
+  MP_REQUIRE(act != ACT_SWIGLU_PAIR || (N % 64 == 0 && !residual), MP_ERR_ARG,
+             "mp_gemv_grouped_w8_bf16: SWIGLU_PAIR needs N %% 64 == 0 and no residual");
+  GroupedArgsW8 a{GemvArgsT<int8_t>{(const bf16_t*)x, ldx, (const int8_t*)W, ldw, strideW, y, ldy, nullptr, (const bf16_t*)residual, ldr, w_index,
+                                    row_scale, row_keep, M, N, K, act, 0, 1.f, scale, strideScale}, E};
+  const int waves = act == ACT_SWIGLU_PAIR ? N / 4 : (int)mp_cdiv(N, 4);
+  const dim3 grid((unsigned)mp_cdiv(waves, 4));
+  if (gv_ksplit_enabled() && act != ACT_SWIGLU_PAIR && N <= 4096 && K >= 4096) {        // gemv_launch's predicate
+    hipLaunchKernelGGL(gemv_grouped_w8_ksplit_kernel, grid, dim3(1024), 0, stream, a);
+    return mp_check_launch("mp_gemv_grouped_w8_bf16(ksplit)");
+  }
+  if (act == ACT_SWIGLU_PAIR) hipLaunchKernelGGL(gemv_grouped_w8_kernel<true>, grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(gemv_grouped_w8_kernel<false>, grid, dim3(256), 0, stream, a);
+  return mp_check_launch("mp_gemv_grouped_w8_bf16");
 }

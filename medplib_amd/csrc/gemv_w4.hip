@@ -7,8 +7,9 @@
 // kernel bodies and the argument block are this file's own, as explicit specialisations of the forms' templates: an NF4 row is two arrays (codes
 // and absmax) and a workgroup needs a lookup table in LDS ahead of its early exits, which the policy interface of gemv_forms.h (a row is one
 // pointer, nothing is set up first) does not carry.  gemv_forms.h and the bf16 and int8 kernels built from it are untouched.
+// The grouped expert form of a batch's rows (mp_gemv_grouped_w4_bf16, one code stream per expert) is at the end of the kernels.
 // Measured: profiles/w4_decode.md.
-#include "gemv_forms.h"
+#include "gemv_grouped.h"
 #include "nf4.h"
 
 namespace {
@@ -270,6 +271,172 @@ MP_W4_SHARED(1, true) MP_W4_SHARED(2, true) MP_W4_SHARED(3, true) MP_W4_SHARED(4
 MP_W4_INDEXED(false, false) MP_W4_INDEXED(false, true) MP_W4_INDEXED(true, false) MP_W4_INDEXED(true, true)
 #undef MP_W4_INDEXED
 
+// ---------------- the GROUPED expert form (mp_gemv_grouped_w4_bf16): the indexed form with one code stream per expert ----------------
+// The rows of a batch that name the same expert share its stream (gemv_grouped.hip: the row sorting is GroupedRows).  Row for row the bits of
+// the indexed form above: nq_fma sums one LOAD's products before the block's absmax is applied, so the load width is part of the arithmetic
+// and stays the indexed form's at every pass size — 16 bytes in the wave form (nq_stream<1, 4>), 8 bytes in the K-split form (nq_stream<1, 2>);
+// the shared form's switch to 8-byte loads at three and four rows is not available here.
+
+// nq_stream over the rows of a pass, which are not equally spaced in memory: the same trips and, per (x row, W row), the same operations.
+template <int NR, int V>
+__device__ __forceinline__ void nq_stream_rows(const uint32_t* __restrict__ tab, const bf16_t* const (&xp)[NR], const Nf4Row (&wp)[4], int k, int kstep,
+                                               int K, float (&acc)[NR][4]) {
+  if (k >= K) return;
+  uint32_t w[4][V];
+  float am[4];
+  uint32_t xs[NR][4 * V];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { nq_ldw<V>(wp[r].c + (k >> 1), w[r]); am[r] = __builtin_nontemporal_load(wp[r].a + (k >> 6)); }
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+#pragma unroll
+    for (int q = 0; q < V; ++q) nq_ldx(xp[j] + k + 8 * q, xs[j], q);
+#pragma unroll 1
+  for (; k < K; k += kstep) {
+    uint32_t wn[4][V];
+    float an[4];
+    uint32_t xn[NR][4 * V];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      an[r] = am[r];
+#pragma unroll
+      for (int q = 0; q < V; ++q) wn[r][q] = w[r][q];
+    }
+#pragma unroll
+    for (int j = 0; j < NR; ++j)
+#pragma unroll
+      for (int q = 0; q < 4 * V; ++q) xn[j][q] = xs[j][q];
+    if (k + kstep < K) {
+      const int kn = k + kstep;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { nq_ldw<V>(wp[r].c + (kn >> 1), wn[r]); an[r] = __builtin_nontemporal_load(wp[r].a + (kn >> 6)); }
+#pragma unroll
+      for (int j = 0; j < NR; ++j)
+#pragma unroll
+        for (int q = 0; q < V; ++q) nq_ldx(xp[j] + kn + 8 * q, xn[j], q);
+    }
+    nq_fma<NR, V>(tab, xs, w, am, acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      am[r] = an[r];
+#pragma unroll
+      for (int q = 0; q < V; ++q) w[r][q] = wn[r][q];
+    }
+#pragma unroll
+    for (int j = 0; j < NR; ++j)
+#pragma unroll
+      for (int q = 0; q < 4 * V; ++q) xs[j][q] = xn[j][q];
+  }
+}
+
+using GroupedArgsW4 = GroupedArgsT<uint8_t>;
+// Passes of two in both forms: a row of x is 32 VGPRs per step in flight with 16-byte loads.  Wave form 199 / 201 VGPRs (two waves per SIMD; with
+// passes of four 256 VGPRs and one wave), K-split form 125 VGPRs (passes of four spilled 152 bytes per lane).  profiles/batch_decode.md.
+#define MP_NQ_WAVE_PASSES MP_GG_PASSES_OF_TWO
+#define MP_NQ_KSPLIT_PASSES MP_GG_PASSES_OF_TWO
+
+template <int NR, bool SWIGLU>
+__device__ __forceinline__ void nq_wave_pass(const uint32_t* tab, const Nf4Args& g, unsigned sel, const Nf4Row (&wp)[4], const int (&rows)[4], int lane) {
+  const bf16_t* xp[NR];
+  gg_x_rows<NR>(g, sel, xp);
+  float acc[NR][4];
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[j][r] = 0.f;
+  nq_stream_rows<NR, 4>(tab, xp, wp, lane * 32, 2048, g.K, acc);
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[j][r] = wave_sum(acc[j][r]);
+  if (lane != 0) return;
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int m = (sel >> (4 * j)) & 15u;
+    if (SWIGLU) {
+      gv_swiglu_store(acc[j], rows, g.N, 1.f, reinterpret_cast<bf16_t*>(g.y) + (int64_t)m * g.ldy);
+    } else {
+      const float scale = gv_row_scale(g, m);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (rows[r] < g.N) gv_store_indexed(g, m, rows[r], acc[j][r], scale);
+    }
+  }
+}
+
+template <bool SWIGLU>
+__global__ __launch_bounds__(256) void gemv_grouped_w4_kernel(GroupedArgsW4 a) {
+  __shared__ uint32_t tab[256];
+  nq_fill(tab);
+  const Nf4Args& g = a.g;
+  const int lane = threadIdx.x & 63;
+  const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
+  int rows[4];
+  gv_wave_rows<SWIGLU>(wid, rows);
+  if (rows[0] >= g.N) return;                             // (no barrier follows)
+  GroupedRows gr(a, lane);
+  if (!SWIGLU && lane < 4 && wid * 4 + lane < g.N) {        // dropped rows: gv_store_dropped (the SwiGLU form leaves them unwritten)
+    for (unsigned long long d = gr.dead; d; d &= d - 1) gv_store_dropped(g, __ffsll((long long)d) - 1, wid * 4 + lane);
+  }
+  while (gr.todo) {
+    int e;
+    unsigned sel;
+    const int cnt = gr.next(e, sel);
+    Nf4Row wp[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wp[r] = nq_row(g, e, min(rows[r], g.N - 1));
+#define MP_NQ_PASS(NR, SEL) nq_wave_pass<NR, SWIGLU>(tab, g, SEL, wp, rows, lane)
+    MP_NQ_WAVE_PASSES(cnt, sel, MP_NQ_PASS);
+#undef MP_NQ_PASS
+  }
+}
+
+template <int NR>
+__device__ __forceinline__ void nq_ksplit_pass(const uint32_t* tab, const Nf4Args& g, unsigned sel, const Nf4Row (&wp)[4], KsplitWave& w,
+                                               float (&red)[4][4][4]) {
+  const bf16_t* xp[NR];
+  gg_x_rows<NR>(g, sel, xp);
+  float acc[NR][4];
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[j][r] = 0.f;
+  nq_stream_rows<NR, 2>(tab, xp, wp, w.lane * 16 + w.kp * 1024, 4096, g.K, acc);
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[j][r] = wave_sum(acc[j][r]);
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int m = (sel >> (4 * j)) & 15u;
+    const float s = w.sum(red, acc[j]);                      // (every wave of the workgroup: the passes are uniform over it)
+    if (w.fin) gv_store_indexed(g, m, w.n, s, gv_row_scale(g, m));
+  }
+}
+
+__global__ __launch_bounds__(1024) void gemv_grouped_w4_ksplit_kernel(GroupedArgsW4 a) {
+  __shared__ uint32_t tab[256];
+  __shared__ float red[4][4][4];
+  nq_fill(tab);
+  const Nf4Args& g = a.g;
+  KsplitWave w(g.N);
+  GroupedRows gr(a, w.lane);
+  if (w.fin) {
+    for (unsigned long long d = gr.dead; d; d &= d - 1) gv_store_dropped(g, __ffsll((long long)d) - 1, w.n);
+  }
+  while (gr.todo) {
+    int e;
+    unsigned sel;
+    const int cnt = gr.next(e, sel);
+    Nf4Row wp[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wp[r] = nq_row(g, e, min(w.row0 + r, g.N - 1));
+#define MP_NQ_PASS(NR, SEL) nq_ksplit_pass<NR>(tab, g, SEL, wp, w, red)
+    MP_NQ_KSPLIT_PASSES(cnt, sel, MP_NQ_PASS);
+#undef MP_NQ_PASS
+  }
+}
+
 // Block-wise absmax quantiser: one workgroup per row, one wave per block of 64 (lane = k inside the block).  absmax = max |w|,
 // inv = absmax > 0 ? 1 / absmax : 0, v = w * inv, code = the number of thresholds strictly below v: every step one fp32 operation in that
 // order.  A zero block gets absmax 0 and codes 7 (v = 0 lies above the seven negative thresholds).  The even k is the high nibble.
@@ -323,4 +490,30 @@ extern "C" int mp_gemv_w4_bf16(const void* x, int64_t ldx, const void* codes, in
                   (const bf16_t*)residual, ldr, w_index, row_scale, row_keep, M, N, K, act, out_dtype == MP_F32, alpha};
   static const char* const names[3] = {"mp_gemv_w4_bf16", "mp_gemv_w4_bf16(indexed)", "mp_gemv_w4_bf16(ksplit)"};
   return gemv_launch<WeightNF4>(g, stream, names);
+}
+
+extern "C" int mp_gemv_grouped_w4_bf16(const void* x, int64_t ldx, const void* codes, int64_t ldw_bytes, int64_t strideW_bytes, const float* absmax,
+                                       int64_t lda, int64_t strideA, void* y, int64_t ldy, const void* residual, int64_t ldr, const int* w_index,
+                                       const float* row_scale, const int* row_keep, int M, int N, int K, int E, int act, hipStream_t stream) {
+  MP_REQUIRE(M >= 1 && M <= GV_MAXM && N > 0 && K > 0 && K % 64 == 0 && ldx % 8 == 0 && E >= 1, MP_ERR_SHAPE,
+             "mp_gemv_grouped_w4_bf16: 1 <= M <= 8, K %% 64 == 0, E >= 1 (M=%d N=%d K=%d E=%d)", M, N, K, E);
+  MP_REQUIRE(ldw_bytes % 16 == 0 && strideW_bytes % 16 == 0 && ldw_bytes >= K / 2, MP_ERR_SHAPE,
+             "mp_gemv_grouped_w4_bf16: ldw_bytes %% 16 == 0 and >= K / 2, strideW_bytes %% 16 == 0 (ldw_bytes=%lld)", (long long)ldw_bytes);
+  MP_REQUIRE(lda >= K / 64, MP_ERR_SHAPE, "mp_gemv_grouped_w4_bf16: lda >= K / 64 (lda=%lld K=%d)", (long long)lda, K);
+  MP_REQUIRE(x && codes && absmax && y && w_index, MP_ERR_ARG,
+             "mp_gemv_grouped_w4_bf16: null operand (the grouped form is the indexed one: w_index is required)");
+  MP_REQUIRE(act == ACT_NONE || act == ACT_SWIGLU_PAIR, MP_ERR_ARG, "mp_gemv_grouped_w4_bf16: only NONE / SWIGLU_PAIR (activation %d)", act);
+  MP_REQUIRE(act != ACT_SWIGLU_PAIR || (N % 64 == 0 && !residual), MP_ERR_ARG,
+             "mp_gemv_grouped_w4_bf16: SWIGLU_PAIR needs N %% 64 == 0 and no residual");
+  const GroupedArgsW4 a{Nf4Args{(const bf16_t*)x, ldx, (const uint8_t*)codes, ldw_bytes, strideW_bytes, absmax, lda, strideA, y, ldy, nullptr,
+                                (const bf16_t*)residual, ldr, w_index, row_scale, row_keep, M, N, K, act, 0, 1.f}, E};
+  const int waves = act == ACT_SWIGLU_PAIR ? N / 4 : (int)mp_cdiv(N, 4);
+  const dim3 grid((unsigned)mp_cdiv(waves, 4));
+  if (gv_ksplit_enabled() && act != ACT_SWIGLU_PAIR && N <= 4096 && K >= 4096) {        // gemv_launch's predicate
+    hipLaunchKernelGGL(gemv_grouped_w4_ksplit_kernel, grid, dim3(1024), 0, stream, a);
+    return mp_check_launch("mp_gemv_grouped_w4_bf16(ksplit)");
+  }
+  if (act == ACT_SWIGLU_PAIR) hipLaunchKernelGGL(gemv_grouped_w4_kernel<true>, grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(gemv_grouped_w4_kernel<false>, grid, dim3(256), 0, stream, a);
+  return mp_check_launch("mp_gemv_grouped_w4_bf16");
 }

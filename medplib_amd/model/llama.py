@@ -36,12 +36,13 @@ def rope_rows_for(n, rows):
 
 # THE table of quantised decode modes, keyed by bit width: what a decode row streams in place of the bf16 weights.  words: the mode in messages;
 # quantizer / gemv: NAMES of ops functions, resolved at call time (tests count calls by patching them on the module); multiple / why: what
-# hidden_size and intermediate_size must be multiples of.  A further mode is one entry here, its ops pair and its pair of public wrappers
+# hidden_size and intermediate_size must be multiples of; gemv_grouped: the NAME of the mode's grouped expert GEMV (the ragged rows of a batch on
+# a top-1 MoE layer: _expert_gemvs_top1).  A further mode is one entry here, its ops triple and its pair of public wrappers
 # (generation.GenerationMixin); nothing else in this file or that one names a bit width.
-DecodeMode = collections.namedtuple("DecodeMode", "bits words quantizer gemv multiple why")
+DecodeMode = collections.namedtuple("DecodeMode", "bits words quantizer gemv multiple why gemv_grouped")
 DECODE_MODES = {m.bits: m for m in (
-    DecodeMode(8, "8-bit", "quantize_rows_w8", "gemv_w8", 16, "16 codes per 16-byte load"),            # row-wise absmax int8, bitsandbytes' weight format: (codes, scale), + half the decoder's bf16 bytes
-    DecodeMode(4, "4-bit", "quantize_blocks_nf4", "gemv_w4", 64, "one absmax per block of 64 weights"),  # NF4: 4-bit codes, one fp32 absmax per 64 weights: (codes, absmax), + 0.28 of them
+    DecodeMode(8, "8-bit", "quantize_rows_w8", "gemv_w8", 16, "16 codes per 16-byte load", "gemv_grouped_w8"),            # row-wise absmax int8, bitsandbytes' weight format: (codes, scale), + half the decoder's bf16 bytes
+    DecodeMode(4, "4-bit", "quantize_blocks_nf4", "gemv_w4", 64, "one absmax per block of 64 weights", "gemv_grouped_w4"),  # NF4: 4-bit codes, one fp32 absmax per 64 weights: (codes, absmax), + 0.28 of them
 )}
 DecodeWeights = collections.namedtuple("DecodeWeights", "mode copies epoch")    # LlamaStack.decode_weights while a mode is on
 
@@ -94,7 +95,7 @@ class LlamaStack:
         self._draws_all = None             # fp32 [L * T * E] gate draws of one pass, all layers: _gate_draws writes and slices
         self.fuse_moe_gather_scatter = True   # top-1, one rank: dispatch / combine folded into the expert GEMMs
         self.fuse_decode_routing = True       # decode rows: post-attention norm + gate + routing in one launch
-        self.group_expert_gemvs = GEMV_GROUPED   # ragged batch rows, top-1, bf16: one weight pass per expert (ops.gemv_grouped), else the indexed form
+        self.group_expert_gemvs = GEMV_GROUPED   # ragged batch rows, top-1: one weight pass per expert (ops.gemv_grouped, or the quantised mode's grouped op), else the indexed form
         self.decode_weights = None         # quantised decode mode: DecodeWeights(mode of DECODE_MODES, per layer {"qkv" | "o" | "gu" | "down": (codes, scales)}, ops.PARAM_EPOCH they were quantised at), or None (off): quantize_decode_weights / drop_decode_weights
         # RoPE in the qkv GEMM's epilogue (mp_gemm_qkv_rope_bf16) wants the q / k head rows interleaved in blocks of 32; the plain
         # fused qkv weight stays (decode GEMVs, the LoRA path's dgrad transposes, export), the interleaved copy (+3.2 GB of 288 at
@@ -278,11 +279,16 @@ class LlamaStack:
     def _expert_gemvs_top1(self, lw, h, x, expert, slot, weight, copies=None, grouped=False):
         """Decode rows, top-1: each row streams its own expert's matrices (GEMV with a device-side expert index); the combine weight, the
         capacity drop and the residual ride in the down projection's epilogue.  Behind _mlp's routing and behind decode_step's fused one.
-        grouped (the ragged rows of a batch, bf16 weights): the rows that name the same expert share its weight pass (ops.gemv_grouped: the
-        indexed form's bits); group_expert_gemvs = False keeps the indexed form (A/B)."""
-        if grouped and copies is None and self.group_expert_gemvs:
-            act = ops.gemv_grouped(h, lw["gu"], expert, act=ops.ACT_SWIGLU_PAIR, row_keep=slot)
-            return ops.gemv_grouped(act, lw["down"], expert, residual=x, row_scale=weight, row_keep=slot)
+        grouped (the ragged rows of a batch): the rows that name the same expert share its weight pass — ops.gemv_grouped on the bf16 weights,
+        the mode's own grouped op (DecodeMode.gemv_grouped) on its quantised copies; each has the bits of the indexed form it replaces;
+        group_expert_gemvs = False keeps the indexed form (A/B), for every weight type."""
+        if grouped and self.group_expert_gemvs:
+            if copies is None:
+                op, gu, down = ops.gemv_grouped, (lw["gu"],), (lw["down"],)
+            else:
+                op, gu, down = getattr(ops, self.decode_weights.mode.gemv_grouped), copies["gu"], copies["down"]
+            act = op(h, *gu, expert, act=ops.ACT_SWIGLU_PAIR, row_keep=slot)
+            return op(act, *down, expert, residual=x, row_scale=weight, row_keep=slot)
         if copies is not None:         # (the quantised gate|up GEMVs also skip a dropped row's weights; its act row stays unwritten and the down projection never reads it)
             act = self._row_proj(lw, "gu", h, copies, act=ops.ACT_SWIGLU_PAIR, w_index=expert, row_keep=slot)
         else:                      # (the bf16 kernel would skip it too, given row_keep; the recorded launch traces pin this call without it)
@@ -531,8 +537,8 @@ class LlamaStack:
         of generate_batch as the rows of one step.  The layer body then takes the unfused qkv branch (the norm-folded launches have no per-row
         twin), ops.decode_rope_append_rows and ops.attention_decode_rows, and routes a MoE layer's rows with a capacity of B and no draws (no
         row is dropped because of its batch-mates: a row's answer does not depend on the others); a top-1 layer's rows share one weight pass
-        per expert (ops.gemv_grouped; the quantised copies keep the indexed form).  NotImplementedError before any state changes where
-        batch_rows_unsupported() says so.
+        per expert (ops.gemv_grouped; under a quantised mode its own grouped op on the copies: ops.gemv_grouped_w8 / _w4).  NotImplementedError
+        before any state changes where batch_rows_unsupported() says so.
         Reproducibility note (round-4 advisor): the narrow projections (o_proj, down) take the K-split GEMV when B == 1 or an expert index is
         given and the shared-weight form otherwise; the two add their partial dot products in different orders, so the SAME prompt decoded at
         batch 1 and at batch 2 may differ in the last fp32 bit of those projections (and, at a near-tie of two logits, in a greedy token).

@@ -416,6 +416,63 @@ def gemv_w4(x, codes, absmax, bias=None, residual=None, act=ACT_NONE, out_dtype=
     return out
 
 
+def _grouped_rows_chk(name, M, N, w_index, residual, row_scale, row_keep):
+    """The row operands of a grouped quantised GEMV (gemv_grouped's checks)."""
+    _chk(w_index, torch.int32, name + ".w_index")
+    assert w_index.shape == (M,) and w_index.stride(0) == 1
+    for t, dt, n in ((row_scale, torch.float32, "row_scale"), (row_keep, torch.int32, "row_keep")):
+        if t is not None:
+            _chk(t, dt, f"{name}.{n}")
+            assert t.shape == (M,) and t.stride(0) == 1
+    if residual is not None:
+        _chk(residual, torch.bfloat16, name + ".residual")
+        assert residual.shape == (M, N) and residual.stride(1) == 1
+
+
+def _grouped_out(name, x, M, N, act, out):
+    cols = N // 2 if act == ACT_SWIGLU_PAIR else N
+    if out is None:
+        out = torch.empty((M, cols), dtype=torch.bfloat16, device=x.device)
+    _chk(out, torch.bfloat16, name + ".out")
+    assert out.shape[0] >= M and out.shape[1] >= cols and out.stride(1) == 1
+    return out
+
+
+def gemv_grouped_w8(x, codes, scale, w_index, residual=None, act=ACT_NONE, row_scale=None, row_keep=None, out=None):
+    """gemv_w8(x, codes, scale, w_index=...) with one code stream per expert instead of one per row (mp_gemv_grouped_w8_bf16): x [M <= 8, K]
+    bf16, codes [E, N, K] int8, scale [E, N] fp32 (quantize_rows_w8), w_index int32 [M] on the device; the rows that name the same expert share
+    its weight pass.  Row for row the bits of gemv_w8() with the same arguments.  act ACT_NONE or ACT_SWIGLU_PAIR; bf16 output.  out (tests):
+    a pre-filled output to write into."""
+    _chk(x, torch.bfloat16, "gemv_grouped_w8.x"); _chk(codes, torch.int8, "gemv_grouped_w8.codes"); _chk(scale, torch.float32, "gemv_grouped_w8.scale")
+    M, K = x.shape
+    assert codes.dim() == 3 and codes.shape[2] == K and x.stride(1) == 1 and codes.stride(-1) == 1
+    assert scale.is_contiguous() and scale.shape == codes.shape[:-1]
+    E, N = codes.shape[0], codes.shape[1]
+    _grouped_rows_chk("gemv_grouped_w8", M, N, w_index, residual, row_scale, row_keep)
+    out = _grouped_out("gemv_grouped_w8", x, M, N, act, out)
+    lib().call("mp_gemv_grouped_w8_bf16", _p(x), x.stride(0), _p(codes), codes.stride(1), codes.stride(0), _p(scale), N, _p(out), out.stride(0),
+               _p(residual), residual.stride(0) if residual is not None else 0, _p(w_index), _p(row_scale), _p(row_keep), M, N, K, E, act, _stream())
+    return out
+
+
+def gemv_grouped_w4(x, codes, absmax, w_index, residual=None, act=ACT_NONE, row_scale=None, row_keep=None, out=None):
+    """gemv_w4(x, codes, absmax, w_index=...) with one code stream per expert instead of one per row (mp_gemv_grouped_w4_bf16): x [M <= 8, K]
+    bf16, codes [E, N, K/2] uint8, absmax [E, N, K/64] fp32 (quantize_blocks_nf4), w_index int32 [M] on the device; the rows that name the same
+    expert share its weight pass.  Row for row the bits of gemv_w4() with the same arguments.  act ACT_NONE or ACT_SWIGLU_PAIR; bf16 output.
+    out (tests): a pre-filled output to write into."""
+    _chk(x, torch.bfloat16, "gemv_grouped_w4.x"); _chk(codes, torch.uint8, "gemv_grouped_w4.codes"); _chk(absmax, torch.float32, "gemv_grouped_w4.absmax")
+    M, K = x.shape
+    assert codes.dim() == 3 and x.stride(1) == 1 and codes.stride(-1) == 1 and codes.shape[-1] * 2 == K
+    assert absmax.stride(-1) == 1 and absmax.shape[:-1] == codes.shape[:-1] and absmax.shape[-1] * 64 == K
+    E, N = codes.shape[0], codes.shape[1]
+    _grouped_rows_chk("gemv_grouped_w4", M, N, w_index, residual, row_scale, row_keep)
+    out = _grouped_out("gemv_grouped_w4", x, M, N, act, out)
+    lib().call("mp_gemv_grouped_w4_bf16", _p(x), x.stride(0), _p(codes), codes.stride(1), codes.stride(0), _p(absmax), absmax.stride(1),
+               absmax.stride(0), _p(out), out.stride(0), _p(residual), residual.stride(0) if residual is not None else 0, _p(w_index),
+               _p(row_scale), _p(row_keep), M, N, K, E, act, _stream())
+    return out
+
+
 def gemm_batched(a, w, out, m_dev=None, bias=None, act=ACT_NONE):
     """a [E,M,K], w [E,N,K], out [E,M,N] (bf16 or f32); m_dev int32 [E] device row counts."""
     _chk(a, torch.bfloat16, "gemm_batched.a"); _chk(w, torch.bfloat16, "gemm_batched.w")

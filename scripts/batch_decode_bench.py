@@ -1,13 +1,14 @@
 """generate_batch() at the 7B dimensions: ragged prompts as the rows of one decode step against the same prompts through generate() one by
-one, and — on the MoE model — against the batch path with the indexed expert GEMVs (MP_GEMV_GROUPED=0: one weight stream per row).
+one, and — on the MoE model, with bf16 weights and under --w8 / --w4 alike — against the batch path with the indexed expert GEMVs
+(MP_GEMV_GROUPED=0: one weight stream per row).
 python scripts/batch_decode_bench.py [--dense] [--w8 | --w4] [--new 64] [--repeats 3] [--rows 1,2,4,8] [--gemv]
 
 Prompts: B texts whose spliced lengths are spread over ~100 positions around 640 (576 image positions + 16..114 text tokens), eos -1.
 Time: device events around the whole call, at 16 and at 16 + --new new tokens; the slope is the step time (prefill and the one-off graph
 capture cancel out), tokens/s = B / step time.  The variants of one B alternate inside every repeat, in one process, after a warm-up of every
 shape; every repeat is printed so that the spread shows.  One JSON line per (B, variant).
---gemv: the expert projections of one layer alone at B = 4 (two rows per expert), grouped against indexed: us per launch and bytes/s of the
-weights the launch has to read (both experts' matrices once)."""
+--gemv: the expert projections of one layer alone at B = 4 (two rows per expert), grouped against indexed, on the weights of the mode that is
+on (bf16, --w8: int8 copies, --w4: NF4 copies): us per launch and bytes/s of the weights the launch has to read (both experts' matrices once)."""
 import argparse
 import json
 import os
@@ -26,8 +27,8 @@ ap.add_argument("--new", type=int, default=64)
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--rows", default="1,2,4,8")
 ap.add_argument("--dense", action="store_true")
-ap.add_argument("--w8", action="store_true", help="8-bit decode weights (the batch path keeps the indexed expert GEMVs)")
-ap.add_argument("--w4", action="store_true", help="4-bit NF4 decode weights (the batch path keeps the indexed expert GEMVs)")
+ap.add_argument("--w8", action="store_true", help="8-bit decode weights (a MoE batch: ops.gemv_grouped_w8)")
+ap.add_argument("--w4", action="store_true", help="4-bit NF4 decode weights (a MoE batch: ops.gemv_grouped_w4)")
 ap.add_argument("--gemv", action="store_true", help="only the expert GEMVs of one layer at B = 4, grouped against indexed")
 args = ap.parse_args()
 assert not (args.w8 and args.w4), "--w8 and --w4 are exclusive"
@@ -57,12 +58,20 @@ if args.gemv:
     expert = torch.tensor([0, 1, 0, 1], dtype=torch.int32, device=dev)
     slot = torch.tensor([0, 0, 1, 1], dtype=torch.int32, device=dev)
     weight = torch.full((4,), 0.75, dtype=torch.float32, device=dev)
+    if args.w8 or args.w4:                  # the mode's copies and its pair of ops (llama.DECODE_MODES)
+        from medplib_amd.model.llama import DECODE_MODES
+        mode = DECODE_MODES[8 if args.w8 else 4]
+        quant, indexed, grouped = (getattr(ops, n) for n in (mode.quantizer, mode.gemv, mode.gemv_grouped))
+        gu, down = quant(gu), quant(down)
+    else:
+        indexed, grouped, gu, down = ops.gemv, ops.gemv_grouped, (gu,), (down,)
     forms = {
-        "gate|up grouped": lambda: ops.gemv_grouped(h, gu, expert, act=ops.ACT_SWIGLU_PAIR, row_keep=slot),
-        "gate|up indexed": lambda: ops.gemv(h, gu, act=ops.ACT_SWIGLU_PAIR, w_index=expert),
-        "down grouped": lambda: ops.gemv_grouped(act_in, down, expert, residual=x, row_scale=weight, row_keep=slot),
-        "down indexed": lambda: ops.gemv(act_in, down, residual=x, w_index=expert, row_scale=weight, row_keep=slot),
+        "gate|up grouped": lambda: grouped(h, *gu, expert, act=ops.ACT_SWIGLU_PAIR, row_keep=slot),
+        "gate|up indexed": lambda: indexed(h, *gu, act=ops.ACT_SWIGLU_PAIR, w_index=expert, **({"row_keep": slot} if len(gu) > 1 else {})),
+        "down grouped": lambda: grouped(act_in, *down, expert, residual=x, row_scale=weight, row_keep=slot),
+        "down indexed": lambda: indexed(act_in, *down, residual=x, w_index=expert, row_scale=weight, row_keep=slot),
     }
+    weight_bytes = lambda ws: sum(t.numel() * t.element_size() for t in ws)                       # noqa: E731  (codes + scales / absmax)
     # the other projection's weights are touched between two launches, so that no launch finds its matrices in the cache
     flush = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
     for name, fn in forms.items():
@@ -72,9 +81,9 @@ if args.gemv:
         for _ in range(20):
             flush.zero_()
             ts.append(timed(fn) * 1e3)
-        nbytes = E * 2 * ff * d * 2 if name.startswith("gate") else E * d * ff * 2
+        nbytes = weight_bytes(gu if name.startswith("gate") else down)
         us = statistics.median(ts)
-        print(json.dumps({"launch": name, "rows": 4, "experts_named": 2, "us_median": round(us, 1), "us_min": round(min(ts), 1), "us_max": round(max(ts), 1),
+        print(json.dumps({"launch": name, "w8": bool(args.w8), "w4": bool(args.w4), "rows": 4, "experts_named": 2, "us_median": round(us, 1), "us_min": round(min(ts), 1), "us_max": round(max(ts), 1),
                           "weight_bytes": nbytes, "TBps_of_those_bytes": round(nbytes / us / 1e6, 2)}))
     sys.exit(0)
 
@@ -115,7 +124,7 @@ def run_single(p, n_new):
 for B in [int(x) for x in args.rows.split(",")]:
     p = prompts(B)
     variants = {"generate_batch": lambda n: run_batch(p, n, True), "generate() one by one": lambda n: run_single(p, n)}
-    if not args.dense and not (args.w8 or args.w4):
+    if not args.dense:
         variants["generate_batch, MP_GEMV_GROUPED=0"] = lambda n: run_batch(p, n, False)
     for fn in variants.values():                      # warm-up of every shape
         fn(BASE)
