@@ -181,6 +181,23 @@ int mp_gemv_top2_gate_up_bf16(const void* x, int64_t ldx, const void* W, int64_t
 int mp_gemv_top2_down_bf16(const void* act, int64_t ldact, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy,
                            const void* residual, int64_t ldr, const int* expert, const int* slot, const float* weight, int tokens, int N,
                            int K, hipStream_t stream);
+/* The top-2 pair with one weight stream per EXPERT instead of one per (token, choice) entry: the entries of a ragged decode batch
+ * (generate_batch) that name the same expert share every loaded W vector, in passes of at most four entries, so a layer reads at most
+ * min(E, 2 * tokens) expert MLPs instead of 2 * tokens.  Arguments and semantics are mp_gemv_top2_gate_up_bf16's / mp_gemv_top2_down_bf16's,
+ * plus E (W [E, N, K]).  gate|up: act[e] = SwiGLU-paired x[e % tokens] . W[expert[e]] for every kept entry; a dropped entry streams nothing and
+ * its act row stays unwritten; an expert no kept entry names streams nothing.  down: y[t] = bf16(residual[t] + acc), acc = 0 then acc =
+ * fma(weight[e], bf16(act[e] . W[expert[e]]), acc) over the kept choices c = 0, 1 of token t in that order (always the sixteen-wave K-split
+ * layout); a token with both choices dropped is bf16(residual + 0), bf16(0) without a residual; the act rows of dropped entries are never read.
+ * Contract: for expert indices in [0, E), entry for entry bit-identical with mp_gemv_top2_gate_up_bf16 / mp_gemv_top2_down_bf16 on the same
+ * arguments (the same per-lane summation order, wave reduction, K-part order, bf16 rounding of the expert output, the combine's two FMAs and
+ * the final rounding).  An entry whose expert index lies outside [0, E) reads no weights and is treated as dropped.  1 <= tokens <= 8,
+ * K % 8 == 0, ld* % 8 == 0, strideW % 8 == 0, E >= 1; gate|up: N % 64 == 0, ldact >= N / 2; down: ldy >= N, ldr >= N with a residual
+ * (MP_ERR_SHAPE); a null operand (MP_ERR_ARG; the residual may be null). */
+int mp_gemv_grouped_top2_gate_up_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* act, int64_t ldact,
+                                      const int* expert, const int* slot, int tokens, int N, int K, int E, hipStream_t stream);
+int mp_gemv_grouped_top2_down_bf16(const void* act, int64_t ldact, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy,
+                                   const void* residual, int64_t ldr, const int* expert, const int* slot, const float* weight, int tokens,
+                                   int N, int K, int E, hipStream_t stream);
 /* mp_rmsnorm_bf16 (HF LlamaRMSNorm, medplib_moe_llama.py:121 / :286) folded into the GEMV that consumes it: y[m, :] = rmsnorm(x[m, :]) @ W^T,
  * bit-identical with the two separate calls.  Decode steps: input_layernorm -> the fused q|k|v projection, and (dense layers)
  * post_attention_layernorm -> the interleaved gate|up projection with act = SWIGLU_PAIR (y [M, N/2]).  1 <= M <= 2; K a multiple of 512

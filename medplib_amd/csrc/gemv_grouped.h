@@ -52,6 +52,16 @@ __device__ __forceinline__ void gg_x_rows(const Args& g, unsigned sel, const bf1
   for (int j = 0; j < NR; ++j) xp[j] = g.x + (int64_t)((sel >> (4 * j)) & 15u) * g.ldx;
 }
 
+// The x rows of a pass over top-2 entries (mp_moe_route_top2's layout, entry e = c * T + t): entry e reads its token's row, e % T.
+template <int NR, class Args>
+__device__ __forceinline__ void gg_x_rows_top2(const Args& g, unsigned sel, int T, const bf16_t* (&xp)[NR]) {
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int m = (sel >> (4 * j)) & 15u;
+    xp[j] = g.x + (int64_t)(m >= T ? m - T : m) * g.ldx;
+  }
+}
+
 // The passes of next() as they come: up to four rows.
 #define MP_GG_PASSES_OF_FOUR(cnt, sel, PASS)       \
   do {                                             \

@@ -10,6 +10,8 @@
 // 2048 s, part_dot's; int8: gq_stream's one FMA per weight at k = 16 lane + 1024 s, or 16 lane + 1024 kp + 4096 s), then wave_sum, then the
 // four K parts in ascending kp (KsplitWave::sum), then the row's scale (int8) and the same epilogues of gemv_epilogue.h.  Only the number of x
 // rows that share a loaded W vector differs.  Measured: profiles/batch_decode.md.
+// The same rule for the top-2 pair (mp_gemv_grouped_top2_gate_up_bf16 / _down_bf16) against gemv_top2_gate_up_kernel / gemv_top2_down_kernel of
+// gemv_bf16.hip: the rows are the 2T (token, choice) entries, and the down kernel combines a token's two expert outputs after the last pass.
 #include "gemv_grouped.h"
 
 namespace {
@@ -58,10 +60,12 @@ __device__ __forceinline__ void gg_dot(const bf16_t* const (&xp)[NR], const bf16
 }
 
 // ---------------- the wave-per-four-rows form (gate|up with SwiGLU; a plain projection outside the K-split shape) ----------------
-template <int NR, bool SWIGLU>
-__device__ __forceinline__ void gg_wave_pass(const GemvArgs& g, unsigned sel, const bf16_t* const (&wp)[4], const int (&rows)[4], int lane) {
+// TOP2: the rows are the 2T (token, choice) entries of mp_moe_route_top2's layout; entry m reads x row m % T and writes output row m.
+template <int NR, bool SWIGLU, bool TOP2>
+__device__ __forceinline__ void gg_wave_pass(const GemvArgs& g, unsigned sel, const bf16_t* const (&wp)[4], const int (&rows)[4], int lane, int T) {
   const bf16_t* xp[NR];
-  gg_x_rows<NR>(g, sel, xp);
+  if constexpr (TOP2) gg_x_rows_top2<NR>(g, sel, T, xp);
+  else gg_x_rows<NR>(g, sel, xp);
   float acc[NR][4];
   if constexpr (NR == 1) WeightBf16::row_dot(xp[0], wp, g.K, lane, acc[0]);      // a lone row: the indexed form's own stream
   else gg_dot<NR>(xp, wp, lane * 8, 512, g.K, acc);
@@ -80,8 +84,8 @@ __device__ __forceinline__ void gg_wave_pass(const GemvArgs& g, unsigned sel, co
   }
 }
 
-template <bool SWIGLU>
-__global__ __launch_bounds__(256) void gemv_grouped_kernel(GroupedArgs a) {
+template <bool SWIGLU, bool TOP2>
+__device__ __forceinline__ void gg_wave_rows_by_expert(const GroupedArgs& a, int T) {
   const GemvArgs& g = a.g;
   const int lane = threadIdx.x & 63;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -101,12 +105,22 @@ __global__ __launch_bounds__(256) void gemv_grouped_kernel(GroupedArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(rows[r], g.N - 1) * g.ldw;
     switch (cnt) {
-      case 1: gg_wave_pass<1, SWIGLU>(g, sel, wp, rows, lane); break;
-      case 2: gg_wave_pass<2, SWIGLU>(g, sel, wp, rows, lane); break;
-      case 3: gg_wave_pass<3, SWIGLU>(g, sel, wp, rows, lane); break;
-      default: gg_wave_pass<4, SWIGLU>(g, sel, wp, rows, lane);
+      case 1: gg_wave_pass<1, SWIGLU, TOP2>(g, sel, wp, rows, lane, T); break;
+      case 2: gg_wave_pass<2, SWIGLU, TOP2>(g, sel, wp, rows, lane, T); break;
+      case 3: gg_wave_pass<3, SWIGLU, TOP2>(g, sel, wp, rows, lane, T); break;
+      default: gg_wave_pass<4, SWIGLU, TOP2>(g, sel, wp, rows, lane, T);
     }
   }
+}
+
+template <bool SWIGLU>
+__global__ __launch_bounds__(256) void gemv_grouped_kernel(GroupedArgs a) {
+  gg_wave_rows_by_expert<SWIGLU, false>(a, 0);
+}
+
+// top-2 gate|up: act[e] = SwiGLU(x[e % T] . W[expert[e]]) for the kept entries e < 2T, the bits of gemv_top2_gate_up_kernel (gemv_bf16.hip)
+__global__ __launch_bounds__(256) void gemv_grouped_top2_gate_up_kernel(GroupedArgs a, int T) {
+  gg_wave_rows_by_expert<true, true>(a, T);
 }
 
 // ---------------- the sixteen-wave K-split form (the experts' down projection: N <= 4096, K >= 4096) ----------------
@@ -146,6 +160,62 @@ __global__ __launch_bounds__(1024) void gemv_grouped_ksplit_kernel(GroupedArgs a
       case 3: gg_ksplit_pass<3>(g, sel, wp, w, red); break;
       default: gg_ksplit_pass<4>(g, sel, wp, w, red);
     }
+  }
+}
+
+// ---------------- top-2 down + combine: gemv_top2_down_kernel (gemv_bf16.hip) with one weight stream per expert ----------------
+// The passes come expert by expert, a token's two choices in different passes, so a finishing lane keeps the bf16-rounded expert output of
+// every entry for its column in LDS (out[entry][column of the workgroup]: it reads only what it wrote itself, no barrier) and combines after
+// the last pass, per token in choice order: acc = 0, acc = fma(weight[e], out[e], acc) for the kept c = 0, 1, then bf16(residual + acc) —
+// the per-entry kernel's two FMAs and rounding.  Every wave builds the same GroupedRows, so every wave reaches every barrier of KsplitWave::sum.
+template <int NR>
+__device__ __forceinline__ void gg_top2_down_pass(const GemvArgs& g, unsigned sel, const bf16_t* const (&wp)[4], KsplitWave& w, float (&red)[4][4][4],
+                                                  float (&out)[2 * GV_MAXM][16]) {
+  const bf16_t* xp[NR];
+  gg_x_rows<NR>(g, sel, xp);                                 // (the x row of entry e is act row e)
+  float acc[NR][4];
+  if constexpr (NR == 1) WeightBf16::part_dot(xp[0], wp, g.K, w.lane, w.kp, acc[0]);      // a lone entry: the per-entry kernel's own stream
+  else gg_dot<NR, false>(xp, wp, w.lane * 8 + w.kp * 512, 2048, g.K, acc);                 // (one step per trip: the 128-VGPR budget)
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int m = (sel >> (4 * j)) & 15u;
+    const float s = w.sum(red, acc[j]);                      // (every wave of the workgroup: the passes are uniform over it)
+    if (w.fin) out[m][w.rg * 4 + w.lane] = (float)(bf16_t)s;
+  }
+}
+
+// Pass width: four entries (one step per trip) fit the sixteen-wave form's 128 VGPRs without scratch, as in gemv_grouped_ksplit_kernel.
+#define MP_GG_TOP2_DOWN_PASSES MP_GG_PASSES_OF_FOUR
+
+__global__ __launch_bounds__(1024) void gemv_grouped_top2_down_kernel(GroupedArgs a, int T) {
+  __shared__ float red[4][4][4];
+  __shared__ float out[2 * GV_MAXM][16];
+  const GemvArgs& g = a.g;
+  KsplitWave w(g.N);
+  GroupedRows gr(a, w.lane);
+  const unsigned long long kept = gr.todo;                   // (wave-uniform, the same in every wave)
+  while (gr.todo) {
+    int e;
+    unsigned sel;
+    const int cnt = gr.next(e, sel);
+    const bf16_t* Wm = g.W + (int64_t)e * g.strideW;
+    const bf16_t* wp[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wp[r] = Wm + (int64_t)min(w.row0 + r, g.N - 1) * g.ldw;
+#define MP_GG_PASS(NR, SEL) gg_top2_down_pass<NR>(g, SEL, wp, w, red, out)
+    MP_GG_TOP2_DOWN_PASSES(cnt, sel, MP_GG_PASS);
+#undef MP_GG_PASS
+  }
+  if (!w.fin) return;                                        // (no barrier follows)
+  const int col = w.rg * 4 + w.lane;
+  for (int t = 0; t < T; ++t) {
+    float acc = 0.f;
+    for (int c = 0; c < 2; ++c) {
+      const int e = c * T + t;
+      if ((kept >> e) & 1) acc = fmaf(g.row_scale[e], out[e][col], acc);
+    }
+    bf16_t* yo = reinterpret_cast<bf16_t*>(g.y) + (int64_t)t * g.ldy;
+    yo[w.n] = g.residual ? (bf16_t)((float)g.residual[(int64_t)t * g.ldr + w.n] + acc) : (bf16_t)acc;
   }
 }
 
@@ -392,4 +462,34 @@ extern "C" int mp_gemv_grouped_w8_bf16(const void* x, int64_t ldx, const void* W
   if (act == ACT_SWIGLU_PAIR) hipLaunchKernelGGL(gemv_grouped_w8_kernel<true>, grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL(gemv_grouped_w8_kernel<false>, grid, dim3(256), 0, stream, a);
   return mp_check_launch("mp_gemv_grouped_w8_bf16");
+}
+
+// The top-2 pair over the 2 * tokens entries of mp_moe_route_top2's layout: mp_gemv_top2_gate_up_bf16 / mp_gemv_top2_down_bf16 (gemv_bf16.hip)
+// with one weight stream per expert; the same checks, and E (an entry whose expert index lies outside [0, E) is a dropped one).
+extern "C" int mp_gemv_grouped_top2_gate_up_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, int64_t strideW, void* act,
+                                                 int64_t ldact, const int* expert, const int* slot, int tokens, int N, int K, int E,
+                                                 hipStream_t stream) {
+  MP_REQUIRE(tokens >= 1 && tokens <= GV_MAXM && N > 0 && N % 64 == 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 &&
+                 strideW % 8 == 0 && ldact >= N / 2 && E >= 1, MP_ERR_SHAPE,
+             "mp_gemv_grouped_top2_gate_up_bf16: 1 <= tokens <= 8, N %% 64 == 0, K %% 8 == 0, ld* %% 8 == 0, ldact >= N / 2, E >= 1 "
+             "(tokens=%d N=%d K=%d E=%d)", tokens, N, K, E);
+  MP_REQUIRE(x && W && act && expert && slot, MP_ERR_ARG, "mp_gemv_grouped_top2_gate_up_bf16: null operand");
+  GroupedArgs a{GemvArgs{(const bf16_t*)x, ldx, (const bf16_t*)W, ldw, strideW, act, ldact, nullptr, nullptr, 0, expert, nullptr, slot,
+                         2 * tokens, N, K, ACT_SWIGLU_PAIR, 0, 1.f}, E};
+  hipLaunchKernelGGL(gemv_grouped_top2_gate_up_kernel, dim3((unsigned)mp_cdiv(N / 4, 4)), dim3(256), 0, stream, a, tokens);
+  return mp_check_launch("mp_gemv_grouped_top2_gate_up_bf16");
+}
+
+extern "C" int mp_gemv_grouped_top2_down_bf16(const void* act, int64_t ldact, const void* W, int64_t ldw, int64_t strideW, void* y, int64_t ldy,
+                                              const void* residual, int64_t ldr, const int* expert, const int* slot, const float* weight,
+                                              int tokens, int N, int K, int E, hipStream_t stream) {
+  MP_REQUIRE(tokens >= 1 && tokens <= GV_MAXM && N > 0 && K > 0 && K % 8 == 0 && ldact % 8 == 0 && ldw % 8 == 0 && strideW % 8 == 0 &&
+                 ldy >= N && (!residual || ldr >= N) && E >= 1, MP_ERR_SHAPE,
+             "mp_gemv_grouped_top2_down_bf16: 1 <= tokens <= 8, K %% 8 == 0, ld* %% 8 == 0, ldy >= N, ldr >= N, E >= 1 (tokens=%d N=%d K=%d E=%d)",
+             tokens, N, K, E);
+  MP_REQUIRE(act && W && y && expert && slot && weight, MP_ERR_ARG, "mp_gemv_grouped_top2_down_bf16: null operand");
+  GroupedArgs a{GemvArgs{(const bf16_t*)act, ldact, (const bf16_t*)W, ldw, strideW, y, ldy, nullptr, (const bf16_t*)residual, ldr, expert, weight,
+                         slot, 2 * tokens, N, K, ACT_NONE, 0, 1.f}, E};
+  hipLaunchKernelGGL(gemv_grouped_top2_down_kernel, dim3((unsigned)mp_cdiv(mp_cdiv(N, 4), 4)), dim3(1024), 0, stream, a, tokens);
+  return mp_check_launch("mp_gemv_grouped_top2_down_bf16");
 }

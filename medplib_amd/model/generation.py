@@ -681,7 +681,8 @@ class GenerationMixin:
         A MoE layer routes every row as generate() does (capacity = the rows of the group, no draws): no row is dropped because of its
         batch-mates, so a row's answer does not depend on the others; the rows of a top-1 layer that name the same expert share one pass over its
         weights — bf16, or the int8 / NF4 copies of the quantised mode that is on (ops.gemv_grouped, ops.gemv_grouped_w8 / _w4: the indexed
-        forms' bits); it is generate()'s function in another summation order (the narrow
+        forms' bits), and so do the (row, choice) entries of a top-2 layer on the bf16 weights (ops.gemv_grouped_top2_gate_up / _down: the
+        per-entry pair's bits, at most min(E, 2 rows) expert MLPs read instead of 2 rows); it is generate()'s function in another summation order (the narrow
         projections of one row take the K-split form, of several the shared one), not its bits.  Same return layout as generate(): prompt
         included, right-padded with eos.  batch_rows = 8: the shared GEMV reads the weights once for up to four rows and twice for five to
         eight, and eight rows still gave more tokens per second than four on the dense and on the MoE model at 7B (profiles/batch_decode.md:

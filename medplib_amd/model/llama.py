@@ -22,8 +22,8 @@ def _rope_tables(seq, head_dim, theta, device, start=0):
     return freqs.cos().contiguous().to(device), freqs.sin().contiguous().to(device)
 
 
-# MP_GEMV_GROUPED=0: the ragged batch rows of a top-1 MoE layer keep the indexed expert GEMVs (one weight stream per row) instead of the grouped
-# form (one per expert): an A/B switch, read once; LlamaStack.group_expert_gemvs starts from it
+# MP_GEMV_GROUPED=0: the ragged batch rows of a MoE layer keep the indexed (top-2: per-entry) expert GEMVs (one weight stream per row or entry)
+# instead of the grouped form (one per expert): an A/B switch, read once; LlamaStack.group_expert_gemvs starts from it
 GEMV_GROUPED = os.environ.get("MP_GEMV_GROUPED", "1") != "0"
 
 ROPE_GROW_ROWS = 1024     # RoPE tables grow in whole multiples of this many rows (slowly lengthening prompts do not reallocate each call)
@@ -95,7 +95,7 @@ class LlamaStack:
         self._draws_all = None             # fp32 [L * T * E] gate draws of one pass, all layers: _gate_draws writes and slices
         self.fuse_moe_gather_scatter = True   # top-1, one rank: dispatch / combine folded into the expert GEMMs
         self.fuse_decode_routing = True       # decode rows: post-attention norm + gate + routing in one launch
-        self.group_expert_gemvs = GEMV_GROUPED   # ragged batch rows, top-1: one weight pass per expert (ops.gemv_grouped, or the quantised mode's grouped op), else the indexed form
+        self.group_expert_gemvs = GEMV_GROUPED   # ragged batch rows: one weight pass per expert (top-1: ops.gemv_grouped, or the quantised mode's grouped op; top-2: ops.gemv_grouped_top2_*), else the indexed / per-entry form
         self.decode_weights = None         # quantised decode mode: DecodeWeights(mode of DECODE_MODES, per layer {"qkv" | "o" | "gu" | "down": (codes, scales)}, ops.PARAM_EPOCH they were quantised at), or None (off): quantize_decode_weights / drop_decode_weights
         # RoPE in the qkv GEMM's epilogue (mp_gemm_qkv_rope_bf16) wants the q / k head rows interleaved in blocks of 32; the plain
         # fused qkv weight stays (decode GEMVs, the LoRA path's dgrad transposes, export), the interleaved copy (+3.2 GB of 288 at
@@ -295,9 +295,18 @@ class LlamaStack:
             act = self._row_proj(lw, "gu", h, copies, act=ops.ACT_SWIGLU_PAIR, w_index=expert)
         return self._row_proj(lw, "down", act, copies, residual=x, w_index=expert, row_scale=weight, row_keep=slot)
 
-    def _expert_gemvs_top2(self, lw, h, x, expert, slot, weight):
+    def _expert_gemvs_top2(self, lw, h, x, expert, slot, weight, grouped=False):
         """Decode rows, top-2: the 2T (token, choice) entries stream their experts' matrices; the down projection adds both weighted expert
-        outputs and the residual in moe_combine's order.  Behind _mlp's routing and behind decode_step's fused one."""
+        outputs and the residual in moe_combine's order.  Behind _mlp's routing and behind decode_step's fused one.
+        grouped (the ragged rows of a batch, two or more): the entries that name the same expert share its weight pass (ops.gemv_grouped_top2_gate_up /
+        _down: at most min(E, 2T) expert MLPs read instead of 2T), with the bits of the per-entry pair; group_expert_gemvs = False keeps
+        the per-entry pair (A/B)."""
+        # A group of one keeps the per-entry pair: its two entries name two different experts, the same two weight streams either way, and the
+        # grouped pair measured no faster there (103.8 against 104.9 us per layer, 5.180 against 5.193 ms per step with a spread of 0.025 in
+        # the per-entry arm's own repeats: profiles/batch_decode.md).  The bits are the same either way.
+        if grouped and self.group_expert_gemvs and h.shape[0] > 1:
+            act = ops.gemv_grouped_top2_gate_up(h, lw["gu"], expert, slot)
+            return ops.gemv_grouped_top2_down(act, lw["down"], expert, slot, weight, x)
         act = ops.gemv_top2_gate_up(h, lw["gu"], expert, slot)
         return ops.gemv_top2_down(act, lw["down"], expert, slot, weight, x)
 
@@ -321,7 +330,7 @@ class LlamaStack:
             return self._expert_gemvs_top1(lw, h, x, expert, slot, weight, copies, grouped=ragged), l_aux, (expert, slot, counts)
         if k == 2 and self._expert_gemv_rows(T):
             expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2(gates, logits, cap, self._gate_draws(i, T, E, True, pass_dev))
-            return self._expert_gemvs_top2(lw, h, x, expert, slot, weight), l_aux, (expert, slot, counts)
+            return self._expert_gemvs_top2(lw, h, x, expert, slot, weight, grouped=ragged), l_aux, (expert, slot, counts)
         if k == 1 and self.ep is None and self.fuse_moe_gather_scatter and not cfg.use_residual:
             return self._mlp_gather_scatter(i, lw, h, x, gates, cap, needed, rstd, pass_dev)
         return self._mlp_dispatch_combine(i, lw, h, x, logits, gates, cap, pass_dev)
@@ -537,7 +546,9 @@ class LlamaStack:
         of generate_batch as the rows of one step.  The layer body then takes the unfused qkv branch (the norm-folded launches have no per-row
         twin), ops.decode_rope_append_rows and ops.attention_decode_rows, and routes a MoE layer's rows with a capacity of B and no draws (no
         row is dropped because of its batch-mates: a row's answer does not depend on the others); a top-1 layer's rows share one weight pass
-        per expert (ops.gemv_grouped; under a quantised mode its own grouped op on the copies: ops.gemv_grouped_w8 / _w4).  NotImplementedError
+        per expert (ops.gemv_grouped; under a quantised mode its own grouped op on the copies: ops.gemv_grouped_w8 / _w4), and so do a top-2
+        layer's 2B (row, choice) entries on the bf16 weights (ops.gemv_grouped_top2_gate_up / _down; B = 1 keeps the per-entry pair, which
+        streams the same two experts).  NotImplementedError
         before any state changes where batch_rows_unsupported() says so.
         Reproducibility note (round-4 advisor): the narrow projections (o_proj, down) take the K-split GEMV when B == 1 or an expert index is
         given and the shared-weight form otherwise; the two add their partial dot products in different orders, so the SAME prompt decoded at
@@ -587,7 +598,7 @@ class LlamaStack:
                 else:
                     draws = self._gate_draws(i, B, E, True, pass_dev)
                     h, expert, slot, weight, _, _, _ = ops.decode_norm_gate_route_top2(x, lw["ln2"], cfg.rms_norm_eps, lw["wg"], cap, draws)
-                    x = self._expert_gemvs_top2(lw, h, x, expert, slot, weight)
+                    x = self._expert_gemvs_top2(lw, h, x, expert, slot, weight, grouped=ragged)
             elif fold and i not in self.moe_layers:
                 # dense layer: post_attention_layernorm inside the gate|up GEMV (same bits as rmsnorm + gemv), then the down projection
                 act = ops.gemv_rmsnorm(x, lw["ln2"], cfg.rms_norm_eps, lw["gu"], act=ops.ACT_SWIGLU_PAIR)

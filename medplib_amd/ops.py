@@ -1866,6 +1866,37 @@ def gemv_top2_down(act, w, expert, slot, weight, residual):
     return out
 
 
+def gemv_grouped_top2_gate_up(h, w, expert, slot):
+    """gemv_top2_gate_up with one weight stream per expert instead of one per (token, choice) entry (mp_gemv_grouped_top2_gate_up_bf16): the
+    entries that name the same expert share its pass, an expert no kept entry names streams nothing.  Kept entries are the bits of
+    gemv_top2_gate_up; an entry whose expert index lies outside [0, E) is treated as dropped.  -> act [2T, ff]."""
+    _chk(h, torch.bfloat16, "gemv_grouped_top2_gate_up.h"); _chk(w, torch.bfloat16, "gemv_grouped_top2_gate_up.w")
+    T, K = h.shape
+    E, N, Kw = w.shape
+    assert Kw == K and h.stride(1) == 1 and w.stride(2) == 1
+    _chk_top2_entries(T, expert, slot)
+    act = torch.empty((2 * T, N // 2), dtype=torch.bfloat16, device=h.device)
+    lib().call("mp_gemv_grouped_top2_gate_up_bf16", _p(h), h.stride(0), _p(w), w.stride(1), w.stride(0), _p(act), act.stride(0), _p(expert),
+               _p(slot), T, N, K, E, _stream())
+    return act
+
+
+def gemv_grouped_top2_down(act, w, expert, slot, weight, residual):
+    """gemv_top2_down with one weight stream per expert (mp_gemv_grouped_top2_down_bf16): the same combine per token, in choice order, on
+    expert outputs computed expert by expert; the bits of gemv_top2_down.  act [2T, ff], w [E, d, ff], residual [T, d] -> out [T, d] bf16."""
+    _chk(act, torch.bfloat16, "gemv_grouped_top2_down.act"); _chk(w, torch.bfloat16, "gemv_grouped_top2_down.w")
+    _chk(residual, torch.bfloat16, "gemv_grouped_top2_down.residual")
+    T2, K = act.shape
+    T = T2 // 2
+    E, N, Kw = w.shape
+    assert T2 == 2 * T and Kw == K and act.stride(1) == 1 and w.stride(2) == 1 and residual.shape == (T, N) and residual.stride(1) == 1
+    _chk_top2_entries(T, expert, slot, weight)
+    out = torch.empty((T, N), dtype=torch.bfloat16, device=act.device)
+    lib().call("mp_gemv_grouped_top2_down_bf16", _p(act), act.stride(0), _p(w), w.stride(1), w.stride(0), _p(out), out.stride(0), _p(residual),
+               residual.stride(0), _p(expert), _p(slot), _p(weight), T, N, K, E, _stream())
+    return out
+
+
 def gather_rows_bf16(src, idx, out=None):
     """out[r] = src[idx[r]]: bf16 rows (src any row stride), idx int64 on the device."""
     _chk(src, torch.bfloat16, "gather_rows_bf16.src")
