@@ -215,6 +215,7 @@ int mp_gemv_rmsnorm_rope_append_bf16(const void* x, int64_t ldx, const float* no
 #define MP_POS_ERR_TABLE 1   /* *pos_dev outside [0, table_rows): no RoPE row */
 #define MP_POS_ERR_CACHE 2   /* *pos_dev outside [0, cache_rows): no KV-cache row */
 #define MP_POS_ERR_BEAM 4    /* beam search: a parent outside [0, nb), or fewer than 2 * nb candidates */
+#define MP_POS_ERR_PICK 8    /* per-row pick (mp_pick_rows_f32): a row's inv_temperature, top_k or top_p is not one a pick accepts */
 /* mp_gemv_rmsnorm_rope_append_bf16 bounded on the device: table_rows = rows of cos_t / sin_t, cache_rows = max_len of the caches, err = an
  * int32 error word in device memory.  When *pos_dev is outside [0, table_rows) or [0, cache_rows) the launch reads no table row and writes
  * nothing (neither q nor the caches) and ORs MP_POS_ERR_TABLE / MP_POS_ERR_CACHE into *err; it does not trap.  In range: the bits of the
@@ -319,6 +320,27 @@ int mp_sample_rows_f32(const float* logits, int64_t ld, int64_t rows, int cols, 
 int mp_sample_filtered_rows_f32(const float* logits, int64_t ld, int64_t rows, int cols, float inv_temperature, int top_k, float top_p,
                                 const float* u, int64_t* out, int* kept /* nullable [rows] */, float* cut /* nullable [rows] */,
                                 hipStream_t stream);
+/* The next-token pick of a batch group whose rows each bring their own parameters: ONE launch, one block per row, and row r gets the token
+ * that the entry point serving its parameters gives on that row alone, bit for bit, whatever rows share the launch:
+ *   inv_temperature[r] == 0: greedy, mp_argmax_rows_f32's token — the first column holding the row's maximum (NaN columns never win).  u[r]
+ *     is not read.  A greedy row without a non-NaN column gives token 0, the sampling kernels' rule for a row with nothing to pick
+ *     (mp_argmax_rows_f32 leaves that case undefined).
+ *   otherwise, filters off (!(0 < top_k[r] < cols) and top_p[r] >= 1): mp_sample_rows_f32 at inv_temperature[r] and u[r], its -inf padding
+ *     and its NaN behaviour included.
+ *   otherwise: mp_sample_filtered_rows_f32 at inv_temperature[r], top_k[r], top_p[r] and u[r] (no kept / cut).
+ * inv_temperature, top_k, top_p and u are [rows] arrays in DEVICE memory, read by the row's block (a block-uniform branch), so a captured
+ * step serves whatever the arrays hold at each replay.  No host read, no workspace, no atomics in any pick: capturable and repeatable.
+ * The host cannot check values it does not read: a row whose inv_temperature is negative, NaN or infinite, whose top_p is outside [0, 1]
+ * or NaN, or whose top_k is negative writes token 0 and ORs MP_POS_ERR_PICK into *err (the sticky int32 error word above, device memory);
+ * the other rows are unaffected.
+ * 0 < cols <= 65536, rows >= 0, and ld >= cols when rows > 1 (there is no ld = 0 form), else MP_ERR_SHAPE; a null operand (rows > 0)
+ * MP_ERR_ARG; both before any launch.  rows == 0 launches nothing. */
+int mp_pick_rows_f32(const float* logits, int64_t ld, int64_t rows, int cols,
+                     const float* inv_temperature,   /* [rows], device; 0 = greedy */
+                     const int* top_k,               /* [rows], device */
+                     const float* top_p,             /* [rows], device */
+                     const float* u,                 /* [rows], device */
+                     int64_t* out, int* err, hipStream_t stream);
 /* One step of beam search over the nb beams' next-token logits (HF 4.31 GenerationMixin.beam_search + BeamSearchScorer.process; what the
  * reference's vqa_infer.py:430-442 asks of generate(num_beams=nb, do_sample=False)).  logits fp32 [nb, cols] with row stride ld; ld = 0: every
  * beam reads the same row (the first step, fed from the prefill's single row).
@@ -572,6 +594,14 @@ int mp_gate_noise_f32(float* out, int64_t n, uint64_t seed, uint64_t offset, int
 /* mp_gate_noise_f32 with the offset read on the device: offset = pass_dev[0] * stride.  A captured decode step keys its draws on a pass
  * counter the graph advances (mp_advance_ints): each replay draws what the host-keyed launch for that pass draws. */
 int mp_gate_noise_dev_f32(float* out, int64_t n, uint64_t seed, const int* pass_dev, uint64_t stride, int gumbel, hipStream_t stream);
+/* The draws of a batch group's rows in one launch, each row under its own seed, seeds and step in device memory: out[r] is exactly what
+ * mp_gate_noise_f32(out, 1, seeds[r], *step_dev, 0) draws — the uniform that picks generated token *step_dev of the request seeded seeds[r]
+ * (values in [2^-25, 1], see mp_sample_rows_f32).  Nothing is read on the host, so a captured decode step that advances *step_dev
+ * (mp_advance_ints) draws at every replay what a token-by-token loop draws for that token, and the seeds may be overwritten between
+ * replays.  *step_dev is taken as unsigned, as mp_gate_noise_dev_f32 takes its pass.  rows >= 0, else MP_ERR_SHAPE; a null operand
+ * (rows > 0) MP_ERR_ARG; rows == 0 launches nothing. */
+int mp_gate_noise_rows_dev_f32(float* out, int64_t rows, const int64_t* seeds /* [rows], device */,
+                               const int* step_dev /* int32 [1], device */, hipStream_t stream);
 /* MOELayer dispatch / combine as index gathers (replaces einsum "sec,sm->ecm" / "sec,ecm->sm"); top_k (1 or 2) entries per
  * token in the layout above. */
 /* Post-attention RMSNorm and the MoE gate in one pass over the rows (LlamaRMSNorm + TopKGate's `logits = x.float() @ wg.float()^T`,

@@ -946,6 +946,14 @@ __global__ void gate_noise_dev_kernel(float* __restrict__ out, int64_t n, unsign
   out[i] = gate_noise_value(seed, (unsigned long long)(unsigned)pass_dev[0] * stride, i, mode);
 }
 
+// One uniform per row of a batch group, each under its own seed: out[r] = the first draw of key (seeds[r], step_dev[0]) — what
+// gate_noise_kernel writes for n = 1, that seed and offset = the step.
+__global__ void gate_noise_rows_dev_kernel(float* __restrict__ out, int64_t rows, const int64_t* __restrict__ seeds, const int* __restrict__ step_dev) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  out[r] = gate_noise_value((unsigned long long)seeds[r], (unsigned long long)(unsigned)step_dev[0], 0, 0);
+}
+
 }  // namespace
 
 extern "C" int mp_cross_entropy_rows_f32(const float* logits, int64_t ld, const int64_t* labels, int64_t n_rows, int vocab,
@@ -1097,6 +1105,14 @@ extern "C" int mp_gate_noise_dev_f32(float* out, int64_t n, uint64_t seed, const
   hipLaunchKernelGGL(gate_noise_dev_kernel, dim3((unsigned)mp_cdiv(n, 256)), dim3(256), 0, stream, out, n, (unsigned long long)seed, pass_dev,
                      (unsigned long long)stride, gumbel ? 1 : 0);
   return mp_check_launch("mp_gate_noise_dev_f32");
+}
+
+extern "C" int mp_gate_noise_rows_dev_f32(float* out, int64_t rows, const int64_t* seeds, const int* step_dev, hipStream_t stream) {
+  MP_REQUIRE(rows >= 0, MP_ERR_SHAPE, "mp_gate_noise_rows_dev_f32: bad size (rows=%lld)", (long long)rows);
+  if (rows == 0) return MP_OK;
+  MP_REQUIRE(out != nullptr && seeds != nullptr && step_dev != nullptr, MP_ERR_ARG, "mp_gate_noise_rows_dev_f32: null operand");
+  hipLaunchKernelGGL(gate_noise_rows_dev_kernel, dim3((unsigned)mp_cdiv(rows, 256)), dim3(256), 0, stream, out, rows, seeds, step_dev);
+  return mp_check_launch("mp_gate_noise_rows_dev_f32");
 }
 
 extern "C" int mp_moe_dispatch_bf16(const void* x, int64_t ldx, const int* expert, const int* slot, void* buf, int64_t ldbuf, int64_t tokens, int dim,

@@ -18,6 +18,7 @@
 #define MP_POS_ERR_TABLE 1         // position outside [0, table_rows): no RoPE row to read
 #define MP_POS_ERR_CACHE 2         // position outside [0, cache_rows): no KV-cache row to write
 #define MP_POS_ERR_BEAM 4          // beam search: a parent outside [0, nb), or fewer than 2 * nb candidates
+#define MP_POS_ERR_PICK 8          // per-row pick: a row's inv_temperature, top_k or top_p is outside what the sampling entry points accept
 #define MP_POS_UNBOUNDED 0x7fffffff   // table_rows / cache_rows of the unbounded entry points
 
 typedef __bf16 bf16_t;

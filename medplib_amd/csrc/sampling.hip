@@ -19,11 +19,11 @@ __device__ __forceinline__ float temperature_weight(float l, float m, float inv_
 // or past `cols` (loaded as -inf) and every column of a row without a maximum above -inf (all -inf, all NaN) weigh 0, whatever they compare
 // equal to: such a row gives 0, and columns past `cols` are never picked.  NaN columns beside finite ones weigh nothing and make C NaN, which
 // ends at the last column with w > 0.
+// (The body is a device function of the block's row r, its draw *u and its token *out: sample_rows_kernel runs it with the launch's one
+// temperature, pick_rows_kernel below with the row's own.)
 template <int K, bool KEEP>
-__global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restrict__ x, int64_t ld, int cols, float inv_t,
-                                                           const float* __restrict__ u, int64_t* __restrict__ out) {
+__device__ __forceinline__ void sample_row(const float* __restrict__ r, int cols, float inv_t, const float* __restrict__ u, int64_t* __restrict__ out) {
   __shared__ float red[16];
-  const float* r = x + (int64_t)blockIdx.x * ld;
   const bool wide = starts_on_16_bytes(r);
   auto piece = [&](int k) { return load_piece(r, wide, cols, -INFINITY, k); };
   float4 v[KEEP ? K : 1];                    // KEEP: the row stays in registers
@@ -45,7 +45,12 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
         p.x = weight(p.x, i); p.y = weight(p.y, i + 1); p.z = weight(p.z, i + 2); p.w = weight(p.w, i + 3);
         return p;
       },
-      u + blockIdx.x, cols, out + blockIdx.x);
+      u, cols, out);
+}
+template <int K, bool KEEP>
+__global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restrict__ x, int64_t ld, int cols, float inv_t,
+                                                           const float* __restrict__ u, int64_t* __restrict__ out) {
+  sample_row<K, KEEP>(x + (int64_t)blockIdx.x * ld, cols, inv_t, u + blockIdx.x, out + blockIdx.x);
 }
 
 // The truncated pick, in the same geometry.  The truncation is a threshold on the logit, `cut`: a column is kept iff l >= cut.
@@ -68,14 +73,13 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
 // every alignment of the row and whatever rows share the launch.
 // Registers: up to 32768 columns the logits stay in registers through both descents, with the survivors' weights beside them in step 3;
 // wider rows are read again from L2 in every round and step 3 evaluates the weights again.
+// (A device function of the block's row as sample_row is: u, out, kept and cut point at the row's own entries, the last three nullable.)
 template <int K, bool KEEP>
-__global__ __launch_bounds__(1024) void sample_filtered_kernel(const float* __restrict__ x, int64_t ld, int cols, float inv_t, int top_k, float top_p,
-                                                               const float* __restrict__ u, int64_t* __restrict__ out, int* __restrict__ kept,
-                                                               float* __restrict__ cut) {
+__device__ __forceinline__ void filtered_row(const float* __restrict__ r, int cols, float inv_t, int top_k, float top_p, const float* __restrict__ u,
+                                             int64_t* __restrict__ out, int* __restrict__ kept, float* __restrict__ cut) {
   __shared__ float red[16];
   __shared__ unsigned red2[2][16];
   const int tid = threadIdx.x;
-  const float* r = x + (int64_t)blockIdx.x * ld;
   const bool wide = starts_on_16_bytes(r);
   auto piece = [&](int k) { return load_piece(r, wide, cols, __uint_as_float(0x7fc00000u), k); };      // columns at or past `cols`: NaN, below every threshold
   int phase = 0;
@@ -93,9 +97,9 @@ __global__ __launch_bounds__(1024) void sample_filtered_kernel(const float* __re
   m = block_max(m, red);
   if (!(m > -INFINITY)) {                    // nothing to keep (block-uniform)
     if (tid == 0) {
-      if (out) out[blockIdx.x] = 0;
-      if (kept) kept[blockIdx.x] = 0;
-      if (cut) cut[blockIdx.x] = INFINITY;
+      if (out) *out = 0;
+      if (kept) *kept = 0;
+      if (cut) *cut = INFINITY;
     }
     return;
   }
@@ -175,12 +179,79 @@ __global__ __launch_bounds__(1024) void sample_filtered_kernel(const float* __re
   }
   const int nkept = count_ge(cutv);
   if (tid == 0) {
-    if (kept) kept[blockIdx.x] = nkept;
-    if (cut) cut[blockIdx.x] = cutv;
+    if (kept) *kept = nkept;
+    if (cut) *cut = cutv;
   }
   if (out == nullptr) return;                // (block-uniform: the launch that only reports kept / cut)
 
-  inverse_cdf_pick<K, KEEP>([&](int k) { return weights_ge(row(k), k, cutv); }, u + blockIdx.x, cols, out + blockIdx.x);
+  inverse_cdf_pick<K, KEEP>([&](int k) { return weights_ge(row(k), k, cutv); }, u, cols, out);
+}
+template <int K, bool KEEP>
+__global__ __launch_bounds__(1024) void sample_filtered_kernel(const float* __restrict__ x, int64_t ld, int cols, float inv_t, int top_k, float top_p,
+                                                               const float* __restrict__ u, int64_t* __restrict__ out, int* __restrict__ kept,
+                                                               float* __restrict__ cut) {
+  const int64_t b = blockIdx.x;
+  filtered_row<K, KEEP>(x + b * ld, cols, inv_t, top_k, top_p, u + b, out ? out + b : nullptr, kept ? kept + b : nullptr, cut ? cut + b : nullptr);
+}
+
+// The greedy row in the same geometry: *out = the first column holding the row's maximum (mp_argmax_rows_f32's token: NaN columns never
+// win, ties go to the smallest index), and 0 for a row without a non-NaN column, the sampling kernels' rule for a row with nothing to pick.
+// Integer compares only: no order to fix.
+template <int K, bool KEEP>
+__device__ __forceinline__ void greedy_row(const float* __restrict__ r, int cols, int64_t* __restrict__ out) {
+  __shared__ float red[16];
+  __shared__ unsigned red2[2][16];
+  const bool wide = starts_on_16_bytes(r);
+  auto piece = [&](int k) { return load_piece(r, wide, cols, -INFINITY, k); };
+  int phase = 0;
+  float4 v[KEEP ? K : 1];
+  constexpr int UN = unroll_of(K, KEEP);
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float4 p = piece(k);
+    if constexpr (KEEP) v[k] = p;
+    m = fmaxf(m, piece_max(p));
+  }
+  m = block_max(m, red);                     // (never NaN: fmaxf drops them; -inf for a row of NaN, which no column equals)
+  int first = 0x7fffffff;
+#pragma unroll UN
+  for (int k = 0; k < K; ++k) {
+    const float4 p = KEEP ? v[KEEP ? k : 0] : piece(k);
+    const int i = piece_column(k);           // (the padding past `cols` is -inf too: the bound keeps it out of an all -inf row's pick)
+    if (p.w == m && i + 3 < cols) first = min(first, i + 3);
+    if (p.z == m && i + 2 < cols) first = min(first, i + 2);
+    if (p.y == m && i + 1 < cols) first = min(first, i + 1);
+    if (p.x == m && i < cols) first = min(first, i);
+  }
+  first = block_all_reduce(first, 0x7fffffff, [](int a, int b) { return min(a, b); }, red2, phase);
+  if (threadIdx.x == 0) *out = first != 0x7fffffff ? first : 0;
+}
+
+// One launch for rows that each bring their own parameters (a batch group's requests): block b reads inv_t[b], top_k[b], top_p[b] from
+// device memory and runs the body of the entry point that serves them on its row alone — greedy_row (inv_t = 0), sample_row (filters off) or
+// filtered_row — so its token has that entry point's bits.  The branch is block-uniform (the values are made scalar first).  A row whose
+// parameters no entry point accepts writes token 0 and ORs MP_POS_ERR_PICK into *err (the error word's own atomic OR, as every kernel that
+// sets it; the picks use none); the other rows do not notice.
+template <int K, bool KEEP>
+__global__ __launch_bounds__(1024) void pick_rows_kernel(const float* __restrict__ x, int64_t ld, int cols, const float* __restrict__ inv_t_rows,
+                                                         const int* __restrict__ top_k_rows, const float* __restrict__ top_p_rows,
+                                                         const float* __restrict__ u, int64_t* __restrict__ out, int* __restrict__ err) {
+  const int64_t b = blockIdx.x;
+  const float inv_t = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(inv_t_rows[b])));
+  const float top_p = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(top_p_rows[b])));
+  const int top_k = __builtin_amdgcn_readfirstlane(top_k_rows[b]);
+  const float* r = x + b * ld;
+  if (!(inv_t >= 0.f && inv_t <= 3.402823466e38f) || !(top_p >= 0.f && top_p <= 1.f) || top_k < 0) {      // (NaN fails both compares)
+    if (threadIdx.x == 0) {
+      out[b] = 0;
+      atomicOr(err, MP_POS_ERR_PICK);
+    }
+    return;
+  }
+  if (inv_t == 0.f) greedy_row<K, KEEP>(r, cols, out + b);
+  else if (!(top_k > 0 && top_k < cols) && top_p >= 1.f) sample_row<K, KEEP>(r, cols, inv_t, u + b, out + b);
+  else filtered_row<K, KEEP>(r, cols, inv_t, top_k, top_p, u + b, out + b, nullptr, nullptr);
 }
 
 }  // namespace
@@ -226,4 +297,20 @@ extern "C" int mp_sample_filtered_rows_f32(const float* logits, int64_t ld, int6
                        top_p, u, tok, kept, cut);
   });
   return mp_check_launch("mp_sample_filtered_rows_f32");
+}
+
+extern "C" int mp_pick_rows_f32(const float* logits, int64_t ld, int64_t rows, int cols, const float* inv_temperature, const int* top_k,
+                                const float* top_p, const float* u, int64_t* out, int* err, hipStream_t stream) {
+  MP_REQUIRE(cols > 0 && cols <= 65536 && rows >= 0, MP_ERR_SHAPE, "mp_pick_rows_f32: bad shape (rows=%lld cols=%d; 0 < cols <= 65536)",
+             (long long)rows, cols);
+  MP_REQUIRE(rows <= 1 || ld >= cols, MP_ERR_SHAPE, "mp_pick_rows_f32: ld=%lld < cols=%d", (long long)ld, cols);
+  if (rows == 0) return MP_OK;
+  MP_REQUIRE(logits != nullptr && inv_temperature != nullptr && top_k != nullptr && top_p != nullptr && u != nullptr && out != nullptr &&
+                 err != nullptr, MP_ERR_ARG, "mp_pick_rows_f32: null operand");
+  for_width(cols, [&](auto shape) {
+    using S = decltype(shape);
+    hipLaunchKernelGGL((pick_rows_kernel<S::K, S::KEEP>), dim3((unsigned)rows), dim3(1024), 0, stream, logits, ld, cols, inv_temperature, top_k,
+                       top_p, u, out, err);
+  });
+  return mp_check_launch("mp_pick_rows_f32");
 }

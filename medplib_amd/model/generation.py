@@ -9,7 +9,9 @@ logits from the prefill and hands the rest to one of two drivers:
 
 A policy says what a step selects and what the host keeps of it: `_single_row_policy` (one sequence, the next token chosen by a pick — the greedy
 argmax or a `_SamplePick`), `_beam_policy` (the num_beams beams of one prompt as the rows of one step) and `_batch_policy` (several prompts of
-different lengths as the rows of one step, each with its own position and key count).  Each is a namespace of closures:
+different lengths as the rows of one step, each with its own position and key count, optionally its own limit and stop ids; picked greedily
+(generate_batch) or by a `_RowsPick`, every row at its own request's sampling parameters: generate_sample_batch, generate_stream_batch).
+Each is a namespace of closures:
 
     first(logits)        the selection of step 0, from the prefill's logits
     step(forward, at)    one decode step: embed the selected ids, forward(emb) -> hidden, logits, selection.  `at` is the device counters of a
@@ -56,6 +58,7 @@ _REFUSED = {
                              "the shipped eval scripts decode greedily",
                  "beams": "beam search (num_beams > 1) is not built here: call generate_beam(); the shipped eval scripts use num_beams=1"},
     "generate_sample": {"beams": "beam search (num_beams > 1) is not built; the shipped eval scripts use num_beams=1"},
+    "generate_sample_batch": {"beams": "beam search per batch row (num_beams > 1) is not built: call generate_beam()"},
     "generate_beam": {"sampling": "beam sampling (do_sample / temperature > 0 with num_beams > 1) is not built"},
     "generate_batch": {"sampling": "sampling per batch row (do_sample / temperature > 0) is not built: the rows of a batch are decoded greedily; "
                                    "call generate_sample()",
@@ -87,6 +90,28 @@ class PromptExtras:
 
 
 NO_EXTRAS = PromptExtras()
+
+
+@dataclasses.dataclass(frozen=True)
+class StreamRequest:
+    """One request of generate_stream_batch: generate_stream()'s arguments that belong to the request.  input_ids [1, L] and images_clip as
+    there; images (the SAM input) with resize_list and original_size_list for the mask of a stopping yield; temperature < 1e-4 is greedy;
+    top_p and top_k count only with apply_top_p; the request stops at eos, at stop_token_id, or when stop_check(ids) is true at a yield."""
+    input_ids: object
+    images_clip: object
+    images: object = None
+    resize_list: object = None
+    original_size_list: object = None
+    region_masks: object = ()
+    valid_region_masks_bool: object = ()
+    temperature: float = 1.0
+    top_p: float = 1.0
+    top_k: int = 0
+    apply_top_p: bool = False
+    max_new_tokens: int = 256
+    stop_token_id: object = None
+    sample_seed: int = 0
+    stop_check: object = None
 
 
 def _argmax_pick(logits, step):
@@ -122,10 +147,43 @@ class _SamplePick:
         return ops.sample_rows_filtered(logits, u, self.temperature, self.top_k, self.top_p)
 
 
+class _RowsPick:
+    """The pick of a batch group whose rows each bring their own request: row b is greedy (temperature None or 0: inv_temperature 0) or
+    drawn at its own temperature, top_k and top_p (0 and 1.0: the plain pick) under its own seed.  One draw launch and one pick launch serve
+    the group (ops.sample_uniform_rows, ops.pick_rows): token `step` of row b is the single-row op of _SamplePick — or ops.argmax_rows — on
+    that row's logits at the keyed draw for (seeds[b], step), bit for bit.  The parameters live in device arrays the launches read, so a
+    captured step holds no request constant.  `step`: an int or the captured step's int32 [1] device counter.  last_u: the [B] draws of the
+    latest step.  err: the int32 [1] word a row with refused parameters sets (POS_ERR_PICK); _batch_policy hands it the cache's."""
+    needs_step = True
+
+    def __init__(self, temperatures, top_ks, top_ps, seeds, device, err=None):
+        inv_t = []
+        for t, k, p in zip(temperatures, top_ks, top_ps):
+            t = 0.0 if t is None else float(t)
+            if not (0.0 <= t < float("inf")) or int(k) < 0 or not 0.0 <= float(p) <= 1.0:
+                raise ValueError(f"sampling: temperature={t} must be finite and not negative, top_k={k} not negative and top_p={p} in [0, 1]")
+            inv_t.append(1.0 / t if t > 0 else 0.0)
+        self.inv_temperature = torch.tensor(inv_t, dtype=torch.float32).to(device)
+        self.top_k = torch.tensor([int(k) for k in top_ks], dtype=torch.int32).to(device)
+        self.top_p = torch.tensor([float(p) for p in top_ps], dtype=torch.float32).to(device)
+        self.seeds = torch.tensor([int(s) for s in seeds], dtype=torch.int64).to(device)
+        self.device, self.err, self.last_u = device, err, None
+
+    def __call__(self, logits, step):
+        if self.err is None:
+            self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        u = ops.sample_uniform_rows(self.seeds, step)
+        self.last_u = u
+        return ops.pick_rows(logits, u, self.inv_temperature, self.top_k, self.top_p, self.err)
+
+
 # ---------------------------------------------------------------------- the two drivers
 def _raise_on_error_word(llm, cache, err, steps=None, S=None, also=""):
-    """The cache's error word (MP_POS_ERR_*) after decode steps: non-zero when a bounded kernel met a position without a table or cache row."""
+    """The cache's error word (MP_POS_ERR_*) after decode steps: non-zero when a bounded kernel met a position without a table or cache row,
+    or (POS_ERR_PICK) when the per-row pick met a row whose parameters no pick accepts."""
     if err:
+        if err & ops.POS_ERR_PICK:
+            also += ", or the per-row pick refused a row's parameters (inv_temperature negative or not finite, top_k < 0, top_p outside [0, 1])"
         if steps is None:
             where = "a decode step"
         elif isinstance(S, (list, tuple)):       # a batch group: every row has its own prompt length
@@ -352,14 +410,23 @@ def _beam_policy(llm, cache, S, max_new_tokens, nb, scorer, eos_token_id, debug,
                                  n_dbg=len(debug) if debug is not None else 0, err_also=err_also)
 
 
-def _batch_policy(llm, hiddens0, cache, lengths, max_new_tokens, stop_ids, pick, debug, captured):
+def _batch_policy(llm, hiddens0, cache, lengths, max_new_tokens, stop_ids, pick, debug, captured, row_limits=None, row_stop_ids=None):
     """The B prompts of a group as the rows of one step: row b sits at its own position lengths[b] + i and sees its own lengths[b] + i + 1 keys
     (decode_step with per-row state); the pick runs over the [B, V] logits; one record of B tokens per step.  At a look the host finds each
     row's first stop id: the call is done when every row has stopped or at max_new_tokens, and what a row computed past its stop is discarded.
     Yields ([generated ids so far per row], [stopped per row], [[hidden states of the prompt, of each fed token] per row]).  hiddens0: the
-    prefill's hidden states per row.  debug: a list that receives (fp32 logits [B, V] on the host, the B tokens) per kept step."""
+    prefill's hidden states per row.  debug: a list that receives (fp32 logits [B, V] on the host, the B tokens) per kept step — with the
+    step's draws (fp32 [B] on the host) between the two when the pick draws (_RowsPick.last_u).
+    row_limits / row_stop_ids: optionally a max_new_tokens (<= max_new_tokens, the largest of them) and a stop-id set per row, in place of
+    the shared ones: a row is finished at its first stop id or at its own limit, what it computes afterwards is discarded, and the group is
+    done when every row is finished."""
     d, dev, B = llm.cfg.hidden_size, llm.device, len(lengths)
     needs_step = getattr(pick, "needs_step", False)
+    limits = [max_new_tokens] * B if row_limits is None else [int(n) for n in row_limits]
+    stops = [stop_ids] * B if row_stop_ids is None else list(row_stop_ids)
+    assert len(limits) == len(stops) == B and all(1 <= n <= max_new_tokens for n in limits)
+    if getattr(pick, "err", False) is None:                   # a pick with an error word of its own to set (_RowsPick): the cache's
+        pick.err = cache["err"]
     st = types.SimpleNamespace(tok=None, logits=None)        # the selected tokens (int64 [B] on the device) and the logits they came from
     generated, hiddens = [], []                               # the loop's record: [B] tokens on the host and [B, 1, d] hidden states per step
     if captured:
@@ -400,16 +467,20 @@ def _batch_policy(llm, hiddens0, cache, lengths, max_new_tokens, stop_ids, pick,
         else:
             generated.append(st.tok.cpu().numpy())
         if debug is not None:
-            debug.append((st.logits.float().cpu(), (toks[i] if captured else st.tok).tolist()))
+            u = getattr(pick, "last_u", None)
+            debug.append((st.logits.float().cpu(),) + (() if u is None else (u.cpu(),)) + ((toks[i] if captured else st.tok).tolist(),))
 
     def kept_rows(ids):
-        """ids [n, B] on the host -> per row the steps kept (up to and including its first stop id) and whether it stopped."""
-        kept, stopped = [], []
+        """ids [n, B] on the host -> per row the steps kept (up to and including its first stop id, its limit at the most), whether it
+        stopped, and whether it is finished (stopped, or at its limit)."""
+        kept, stopped, finished = [], [], []
         for b in range(B):
-            hits = [i for i, t in enumerate(ids[:, b].tolist()) if t in stop_ids]
-            kept.append(hits[0] + 1 if hits else ids.shape[0])
+            own = ids[:limits[b], b].tolist()
+            hits = [i for i, t in enumerate(own) if t in stops[b]]
+            kept.append(hits[0] + 1 if hits else len(own))
             stopped.append(bool(hits))
-        return kept, stopped
+            finished.append(bool(hits) or len(own) == limits[b])
+        return kept, stopped, finished
 
     def out_of(ids, kept, stopped, hidden_of):
         return ([ids[:kept[b], b].tolist() for b in range(B)], stopped,
@@ -417,13 +488,13 @@ def _batch_policy(llm, hiddens0, cache, lengths, max_new_tokens, stop_ids, pick,
 
     def look(got, upto):
         ids = got.view(np.int64).reshape(upto, B)
-        kept, stopped = kept_rows(ids)
-        return max(kept), all(stopped), out_of(ids, kept, stopped, lambda i, b: hid_all[i, b].view(1, 1, d))
+        kept, stopped, finished = kept_rows(ids)
+        return max(kept), all(finished), out_of(ids, kept, stopped, lambda i, b: hid_all[i, b].view(1, 1, d))
 
     def loop_look(i):
         ids = np.stack(generated)
-        kept, stopped = kept_rows(ids)
-        finished = all(stopped) or len(generated) == max_new_tokens
+        kept, stopped, done = kept_rows(ids)
+        finished = all(done) or len(generated) == max_new_tokens
         if finished:
             _raise_on_error_word(llm, cache, int(cache["err"][0]))
         return finished, out_of(ids, kept, stopped, lambda j, b: hiddens[j][b].view(1, 1, d))
@@ -619,14 +690,15 @@ class GenerationMixin:
         policy = _single_row_policy(self.model.llm, hidden, cache, max_new_tokens, stop_ids, pick, debug, captured)
         yield from self._drive(policy, hidden, cache, S, max_new_tokens, captured, looks)
 
-    def _decode_batch(self, prompts, max_new_tokens, stop_ids, pick=_argmax_pick, looks=None, debug=None):
+    def _decode_batch(self, prompts, max_new_tokens, stop_ids, pick=_argmax_pick, looks=None, debug=None, row_limits=None, row_stop_ids=None):
         """_decode for the prompts of one batch group, (ids, images_clip, extras) each, as the rows of one decode step (_batch_policy): every
         prompt prefilled at batch 1 into its row of one cache, then single-token steps at B rows with a position and a key count per row,
         the next tokens chosen by `pick` over the [B, V] logits.  Through the captured graph under _decode's conditions, else token by token.
-        A generator of ([generated ids so far per row], [stopped per row], [[hidden states of the prompt, of each fed token] per row])."""
+        A generator of ([generated ids so far per row], [stopped per row], [[hidden states of the prompt, of each fed token] per row]).
+        row_limits / row_stop_ids: a max_new_tokens and a stop-id set per row (_batch_policy)."""
         hiddens, cache, lengths = self._prefill_batch(prompts, max_new_tokens)
         captured = self._captures(max_new_tokens)
-        policy = _batch_policy(self.model.llm, hiddens, cache, lengths, max_new_tokens, stop_ids, pick, debug, captured)
+        policy = _batch_policy(self.model.llm, hiddens, cache, lengths, max_new_tokens, stop_ids, pick, debug, captured, row_limits, row_stop_ids)
         last = torch.cat([h[0, -1:] for h in hiddens])
         yield from self._drive(policy, last, cache, lengths, max_new_tokens, captured, looks)      # (S: the error message's positions, per row)
 
@@ -700,18 +772,22 @@ class GenerationMixin:
         return self._generate_groups(input_ids, images, attention_mask, max_new_tokens, eos_token_id, n_rows, kwargs, _argmax_pick)
 
     @torch.no_grad()
-    def _generate_groups(self, input_ids, images, attention_mask, max_new_tokens, eos_token_id, n_rows, kwargs, pick):
+    def _generate_groups(self, input_ids, images, attention_mask, max_new_tokens, eos_token_id, n_rows, kwargs, pick, pick_of_group=None,
+                         who="generate_batch", debug=None):
         """generate_batch() behind its argument checks: the rows in groups of n_rows through _decode_batch, the next tokens chosen by
-        pick(logits [B, V], step) -> int64 [B]; output ids [B, L + n_max], prompt included, right-padded with eos."""
+        pick(logits [B, V], step) -> int64 [B] — or, with pick_of_group(first row, rows) -> pick, by a pick made for each group (the rows'
+        own sampling parameters); output ids [B, L + n_max], prompt included, right-padded with eos."""
         ids = _np_ids(input_ids).astype(np.int64)
         rows = []
-        with self._decoding("generate_batch"):
+        with self._decoding(who):
             prompts = [_row_prompt(ids, images, attention_mask, kwargs, b) for b in range(ids.shape[0])]
             for g0 in range(0, len(prompts), n_rows):
                 group = prompts[g0:g0 + n_rows]
                 generated = [[] for _ in group]
+                if pick_of_group is not None:
+                    pick = pick_of_group(g0, len(group))
                 # (closed before the prologue is undone: the driver's `finally` settles the pass counter)
-                with contextlib.closing(self._decode_batch(group, max_new_tokens, (eos_token_id,), pick=pick)) as steps:
+                with contextlib.closing(self._decode_batch(group, max_new_tokens, (eos_token_id,), pick=pick, debug=debug)) as steps:
                     for generated, _, _ in steps:
                         pass
                 rows += [np.concatenate([p[0][0], np.asarray(g, dtype=np.int64)]) for p, g in zip(group, generated)]
@@ -740,6 +816,55 @@ class GenerationMixin:
             return self._greedy(row, img, max_new_tokens, eos_token_id, extras, pick=pick)[0]
 
         return self._generate_rows("generate_sample", input_ids, images, attention_mask, max_new_tokens, eos_token_id, kwargs, decode_row)
+
+    @torch.no_grad()
+    def generate_sample_batch(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, temperature=1.0, top_k=50,
+                              top_p=1.0, sample_seed=None, batch_rows=8, **kwargs):
+        """generate_sample() with the rows decoded TOGETHER, as generate_batch() decodes generate()'s: the rows are taken in groups of
+        `batch_rows` (1..8, else ValueError) and a group is the rows of one decode step, drawn and picked by one launch each (_RowsPick:
+        ops.sample_uniform_rows, ops.pick_rows).  temperature, top_k and top_p are scalars or one value per row (a sequence of another length:
+        ValueError), so rows of one step may sample differently; row b draws under sample_seed + b, generate_sample()'s rule, and
+        sample_seed=None takes a seed from torch's global generator.  Same return layout: prompt included, right-padded with eos.
+        A row is generate_sample()'s function in another summation order, as a generate_batch row is generate()'s — not its tokens.  What IS
+        exact: token i of row b is the single-row op (ops.sample_rows / ops.sample_rows_filtered, by generate_sample()'s rule) on that step's
+        own logits row at the draw for (sample_seed + b, i).  ValueError for a temperature that is not > 0 and for do_sample=False;
+        NotImplementedError, before any state changes, for beams and wherever generate_batch() refuses the model (gate sampling or an
+        injected draw provider, the residual MoE, expert parallelism).  debug: a list that receives (fp32 logits [B, V], u [B], tokens [B])
+        per kept step of every group (tests; costs a sync per token)."""
+        debug = kwargs.pop("debug", None)
+        n_prompts = int(_np_ids(input_ids).shape[0])
+
+        def per_row(value, name, cast):
+            if isinstance(value, (list, tuple, np.ndarray)) or torch.is_tensor(value):
+                if len(value) != n_prompts:
+                    raise ValueError(f"generate_sample_batch(): {name} has {len(value)} entries for {n_prompts} rows (a scalar, or one per row)")
+                return [cast(v) for v in value]
+            return [cast(value)] * n_prompts
+
+        temperatures = per_row(temperature, "temperature", float)
+        top_ks = per_row(top_k, "top_k", lambda k: int(k or 0))
+        top_ps = per_row(top_p, "top_p", lambda p: 1.0 if p is None else float(p))
+        for t in temperatures:
+            if not t > 0:
+                raise ValueError(f"generate_sample_batch(): temperature={t} has to be a strictly positive float (greedy decoding: generate_batch())")
+        _check_kwargs("generate_sample_batch", kwargs)
+        if kwargs.get("do_sample") is False:
+            raise ValueError("generate_sample_batch(): do_sample=False asks for greedy decoding: call generate_batch()")
+        n_rows, max_new_tokens = int(batch_rows), int(max_new_tokens)
+        if not 1 <= n_rows <= 8:
+            raise ValueError(f"generate_sample_batch(): batch_rows={batch_rows} must lie in 1..8 (the rows of one decode step)")
+        assert max_new_tokens >= 1
+        why = self.model.llm.batch_rows_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"generate_sample_batch(): {why}: call generate_sample()")
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,))) if sample_seed is None else int(sample_seed)
+
+        def pick_of_group(g0, n):
+            rows = slice(g0, g0 + n)
+            return _RowsPick(temperatures[rows], top_ks[rows], top_ps[rows], [seed + b for b in range(g0, g0 + n)], self.device_)
+
+        return self._generate_groups(input_ids, images, attention_mask, max_new_tokens, eos_token_id, n_rows, kwargs, None,
+                                     pick_of_group=pick_of_group, who="generate_sample_batch", debug=debug)
 
     @torch.no_grad()
     def generate_beam(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, num_beams=4, length_penalty=1.0,
@@ -830,6 +955,71 @@ class GenerationMixin:
                         pred_mask = self._seg_mask(output_ids, list(hiddens), images, resize_list, original_size_list)[0]
                     yield new, stopped, pred_mask
                     if stopped or i == max_new_tokens - 1:
+                        break
+
+    def generate_stream_batch(self, requests, stream_interval=1, eos_token_id=2, debug=None):
+        """generate_stream() for 1 to 8 requests (StreamRequest; more: ValueError) as the rows of ONE decode step: the group pays one pass
+        over the decoder weights per token, and every row is drawn and picked at its own request's parameters by one launch each (_RowsPick).
+        Per request the meaning is generate_stream()'s: temperature < 1e-4 is greedy, top_p and top_k count only with apply_top_p, and the
+        request stops at eos_token_id, at its stop_token_id, or when its stop_check(ids) is true at a yield.
+        A generator of (row, new token ids so far, stopped, pred_mask): row r yields after its tokens i with i % stream_interval == 0, after
+        its own last token (i == its max_new_tokens - 1) and at its stop; every yield's ids are a prefix of the row's next one, and nothing
+        is yielded for a row after it has finished.  The group ends when every row has.  pred_mask is _seg_mask on that row's own ids and
+        hidden states and appears only in its stopping yield, under generate_stream()'s conditions (the request has `images`, a generated id
+        is seg_token_idx; an answer that runs into its limit gets none).
+        Decode path (last_decode_path): the captured graph under generate_batch()'s conditions, else the loop; the host looks at the ids every
+        stream_interval steps (and at the rows' last tokens).  A row is generate_stream()'s function in another summation order; exact is what
+        generate_sample_batch() states: every token is the single-row op on its step's own logits row at the draw for (sample_seed, i).
+        `uniforms` injection is not offered.  NotImplementedError, before any state changes, wherever generate_batch() refuses the model.
+        debug: a list that receives (fp32 logits [B, V], u [B], tokens [B]) per kept step (tests; costs a sync per token)."""
+        requests = list(requests)
+        if not 1 <= len(requests) <= 8:
+            raise ValueError(f"generate_stream_batch(): {len(requests)} requests: 1 to 8 are the rows of one decode step")
+        why = self.model.llm.batch_rows_unsupported()
+        if why is not None:
+            raise NotImplementedError(f"generate_stream_batch(): {why}: call generate_stream() per request")
+        limits = [int(r.max_new_tokens) for r in requests]
+        assert min(limits) >= 1
+        greedy = [r.temperature < 1e-4 for r in requests]
+        filtered = [r.apply_top_p and not g for r, g in zip(requests, greedy)]
+        pick = _RowsPick([None if g else r.temperature for r, g in zip(requests, greedy)],
+                         [int(r.top_k or 0) if f else 0 for r, f in zip(requests, filtered)],
+                         [(1.0 if r.top_p is None else float(r.top_p)) if f else 1.0 for r, f in zip(requests, filtered)],
+                         [r.sample_seed for r in requests], self.device_)
+        return self._stream_batch(requests, limits, pick, max(1, int(stream_interval)), eos_token_id, debug)
+
+    @torch.no_grad()
+    def _stream_batch(self, requests, limits, pick, every, eos_token_id, debug):
+        """generate_stream_batch() behind its argument checks."""
+        with self._decoding("generate_stream_batch"):
+            B, n_max = len(requests), max(limits)
+            prompts, stops = [], []
+            for r in requests:
+                ids = _np_ids(r.input_ids).astype(np.int64)
+                assert ids.shape[0] == 1, "a StreamRequest holds one sample"
+                prompts.append((ids, r.images_clip, PromptExtras(region_masks=r.region_masks, valid_region_masks_bool=r.valid_region_masks_bool)))
+                stops.append({int(t) for t in (eos_token_id, r.stop_token_id) if t is not None})
+            due = lambda i, b: i % every == 0 or i == limits[b] - 1            # noqa: E731  generate_stream's condition, on the row's own limit
+            looks = sorted({i + 1 for i in range(n_max) if i % every == 0} | set(limits))
+            finished, sent = [False] * B, [0] * B
+            with contextlib.closing(self._decode_batch(prompts, n_max, (), pick=pick, looks=looks, debug=debug, row_limits=limits,
+                                                       row_stop_ids=stops)) as steps:
+                for generated, stopped_rows, hiddens in steps:
+                    for b, r in enumerate(requests):
+                        new = list(generated[b])
+                        i, stopped = len(new) - 1, stopped_rows[b]
+                        if finished[b] or len(new) == sent[b] or not (stopped or due(i, b)):
+                            continue
+                        sent[b] = len(new)
+                        if not stopped and r.stop_check is not None and r.stop_check(new):
+                            stopped = True
+                        pred_mask = None
+                        if stopped and r.images is not None and self.seg_token_idx in new:
+                            output_ids = np.concatenate([prompts[b][0], np.asarray(new, dtype=np.int64)[None]], 1)
+                            pred_mask = self._seg_mask(output_ids, list(hiddens[b]), r.images, r.resize_list, r.original_size_list)[0]
+                        finished[b] = stopped or i == limits[b] - 1
+                        yield b, new, stopped, pred_mask
+                    if all(finished):
                         break
 
     # ------------------------------------------------------------------ evaluate (MedPLIB.py:574-680)

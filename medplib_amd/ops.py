@@ -1119,7 +1119,43 @@ def sample_uniform_dev(seed, step_dev, device):
     return gate_noise_dev(1, seed, step_dev, 1, False, device)
 
 
+def sample_uniform_rows(seeds, step):
+    """sample_uniform for the rows of a batch group in one launch (mp_gate_noise_rows_dev_f32): out[r] = sample_uniform(seeds[r], step)[0].
+    seeds int64 [rows] on the device; step an int32 [1] device counter (a captured step: every replay draws at what the counter holds) or an
+    int, wrapped into one.  -> fp32 [rows]."""
+    _chk(seeds, torch.int64, "sample_uniform_rows.seeds")
+    assert seeds.dim() == 1 and seeds.is_contiguous()
+    if not torch.is_tensor(step):
+        step = torch.tensor([int(step)], dtype=torch.int32, device=seeds.device)
+    _chk(step, torch.int32, "sample_uniform_rows.step")
+    assert step.numel() == 1
+    out = torch.empty(seeds.numel(), dtype=torch.float32, device=seeds.device)
+    lib().call("mp_gate_noise_rows_dev_f32", _p(out), seeds.numel(), _p(seeds), _p(step), _stream())
+    return out
+
+
 POS_ERR_BEAM = 4          # MP_POS_ERR_BEAM: a parent outside [0, nb), or fewer than 2 * nb candidates
+POS_ERR_PICK = 8          # MP_POS_ERR_PICK: a row of pick_rows whose inv_temperature, top_k or top_p no pick accepts
+
+
+def pick_rows(logits, u, inv_temperature, top_k, top_p, err):
+    """The next tokens of rows that each bring their own parameters, in one launch (mp_pick_rows_f32): row r is argmax_rows where
+    inv_temperature[r] == 0 (u[r] unread; a row without a non-NaN column: 0), sample_rows where its filters are off (not 0 < top_k[r] < cols,
+    top_p[r] >= 1) and sample_rows_filtered otherwise, at 1 / inv_temperature[r] — that op's token on the row alone, bit for bit.  logits fp32
+    [rows, cols]; u, inv_temperature, top_p fp32 [rows] and top_k int32 [rows] on the device, read there: a captured launch serves what they
+    hold at each replay.  A row with parameters no pick accepts gives 0 and POS_ERR_PICK in err (int32 [1]: the KV cache's error word).
+    -> int64 [rows]."""
+    _chk(logits, torch.float32, "pick_rows.logits"); _chk(u, torch.float32, "pick_rows.u")
+    _chk(inv_temperature, torch.float32, "pick_rows.inv_temperature"); _chk(top_k, torch.int32, "pick_rows.top_k")
+    _chk(top_p, torch.float32, "pick_rows.top_p"); _chk(err, torch.int32, "pick_rows.err")
+    assert logits.dim() == 2 and logits.stride(1) == 1 and err.numel() == 1
+    rows = logits.shape[0]
+    for t_ in (u, inv_temperature, top_k, top_p):
+        assert t_.dim() == 1 and t_.is_contiguous() and t_.numel() == rows
+    out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    lib().call("mp_pick_rows_f32", _p(logits), logits.stride(0), rows, logits.shape[1], _p(inv_temperature), _p(top_k), _p(top_p), _p(u),
+               _p(out), _p(err), _stream())
+    return out
 
 
 def beam_topk(logits, beam_scores, eos_id, cand_score, cand_index, next_scores, next_tokens, next_parent, err, nb=None):

@@ -16,8 +16,18 @@ the reference, and every request takes its sampling seed from torch's global gen
 optional top_k (default 0: none) truncate the distribution before the draw — HF's top-k, then top-p, in the same captured step
 (ops.sample_rows_filtered); without the flag a request is served exactly as the reference serves it.
 
+Several requests at once: `ModelWorker.generate_stream_gate_batch(params_list)` serves the requests a server holds in list order in groups
+of min(8, --limit-model-concurrency) — the requests of a group are the rows of ONE decode step (`MedPLIBForCausalLM.generate_stream_batch`:
+one pass over the weights per token for the group, every row drawn and picked at its own temperature, top_p / top_k, seed, max_new_tokens
+and stop) — and yields (index in params_list, message bytes), every message in generate_stream's format.  Both loops parse a request with
+one helper (`_request`) and build a message with one (`_message`); seeds are drawn from torch's global generator in list order.  Where the
+model refuses batch rows — moe_gate_sampling (the gate's draws are keyed on the rows of one pass), the residual MoE, expert parallelism —
+the batch loop falls back to one request at a time through `generate_stream`, in the same (index, message) shape.  The shipped 7B config
+has moe_gate_sampling ON: such a model is served one by one until it is switched off.
+
 Out of scope: the HTTP server (FastAPI / uvicorn), the controller registration, the heartbeat thread and the concurrency semaphore;
---limit-model-concurrency is parsed and carried for a server built around `ModelWorker.generate_stream_gate`.
+--limit-model-concurrency is parsed and sizes the groups of `generate_stream_gate_batch` for a server built around it or around
+`ModelWorker.generate_stream_gate`.
 
 `images` / `region_masks` of a request: base64 strings as the reference's clients send them (decoded with Pillow, which is imported only then)
 or uint8 arrays ([H, W, 3] RGB, [H, W]).  --load-8bit (reference :72,100,642 -> builder.py:39, bitsandbytes) is a SPEED mode here, not a memory mode:
@@ -29,6 +39,7 @@ import base64
 import io
 import json
 import sys
+import types
 from pathlib import Path
 
 import numpy as np
@@ -161,9 +172,11 @@ class ModelWorker:
             grids.append(m[::self.patch, ::self.patch].contiguous())
         return [grids], [[torch.ones(1).bool()]]
 
-    @torch.no_grad()
-    def generate_stream(self, params):
-        tok, model = self.tokenizer, self.model
+    def _request(self, params):
+        """One request's params -> what both token loops need: the images and regions, temperature / top_p / top_k, max_new_tokens (capped),
+        the stop string and its one-id form, the prompt's ids cut to the context, and a sampling seed from torch's global generator (drawn
+        last: requests parsed in list order draw their seeds in list order)."""
+        tok = self.tokenizer
         prompt = params["prompt"]
         clip, sam, resize_list, original_size_list = self._images(params)
         if clip is None:
@@ -188,22 +201,70 @@ class ModelWorker:
         def stop_seen(ids):
             return bool(stop_str) and decode(ids).rfind(stop_str) != -1
 
-        for new_ids, stopped, pred_mask in model.generate_stream(
-                np.asarray([input_ids], dtype=np.int64), clip, images=sam, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,
-                stop_token_id=stop_idx, eos_token_id=tok.eos_token_id, stream_interval=self.args.stream_interval,
-                sample_seed=int(torch.randint(0, 2 ** 31 - 1, (1,))), resize_list=resize_list, original_size_list=original_size_list,
-                region_masks=region_masks, valid_region_masks_bool=region_valid, stop_check=stop_seen, top_k=top_k, apply_top_p=apply_top_p):
-            text = decode(new_ids)
-            if stop_str:
-                pos = text.rfind(stop_str)
-                if pos != -1:
-                    text = text[:pos]
-            mask, height, width = [], 0, 0
-            if pred_mask is not None:
-                m = (torch.sigmoid(pred_mask.float()) > MASK_THRESHOLD).int().squeeze(0).cpu().numpy()
-                height, width = m.shape
-                mask = encode_sparse(m)
-            yield json.dumps({"text": prompt + text, "mask": mask, "height": str(height), "width": str(width), "error_code": 0}).encode() + b"\0"
+        return types.SimpleNamespace(
+            prompt=prompt, clip=clip, sam=sam, resize_list=resize_list, original_size_list=original_size_list, region_masks=region_masks,
+            region_valid=region_valid, temperature=temperature, top_p=top_p, apply_top_p=apply_top_p, top_k=top_k, max_new_tokens=max_new_tokens,
+            stop_str=stop_str, stop_idx=stop_idx, input_ids=np.asarray([input_ids], dtype=np.int64), decode=decode, stop_seen=stop_seen,
+            seed=int(torch.randint(0, 2 ** 31 - 1, (1,))))
+
+    @staticmethod
+    def _message(rq, new_ids, pred_mask):
+        """One message of a request: the prompt and the text so far, cut at the last occurrence of the stop string, and the sparse mask."""
+        text = rq.decode(new_ids)
+        if rq.stop_str:
+            pos = text.rfind(rq.stop_str)
+            if pos != -1:
+                text = text[:pos]
+        mask, height, width = [], 0, 0
+        if pred_mask is not None:
+            m = (torch.sigmoid(pred_mask.float()) > MASK_THRESHOLD).int().squeeze(0).cpu().numpy()
+            height, width = m.shape
+            mask = encode_sparse(m)
+        return json.dumps({"text": rq.prompt + text, "mask": mask, "height": str(height), "width": str(width), "error_code": 0}).encode() + b"\0"
+
+    def _stream_one(self, rq):
+        """The messages of one parsed request through the model's generate_stream."""
+        for new_ids, stopped, pred_mask in self.model.generate_stream(
+                rq.input_ids, rq.clip, images=rq.sam, temperature=rq.temperature, top_p=rq.top_p, max_new_tokens=rq.max_new_tokens,
+                stop_token_id=rq.stop_idx, eos_token_id=self.tokenizer.eos_token_id, stream_interval=self.args.stream_interval,
+                sample_seed=rq.seed, resize_list=rq.resize_list, original_size_list=rq.original_size_list,
+                region_masks=rq.region_masks, valid_region_masks_bool=rq.region_valid, stop_check=rq.stop_seen, top_k=rq.top_k,
+                apply_top_p=rq.apply_top_p):
+            yield self._message(rq, new_ids, pred_mask)
+
+    @torch.no_grad()
+    def generate_stream(self, params):
+        yield from self._stream_one(self._request(params))
+
+    @torch.no_grad()
+    def generate_stream_batch(self, params_list):
+        """The requests a server holds, served together: taken in order in groups of min(8, --limit-model-concurrency), each group the rows
+        of one decode step (MedPLIBForCausalLM.generate_stream_batch).  Yields (index in params_list, message bytes); per index the messages
+        are generate_stream's: the text cut at the stop string, the sparse mask with the stopping message, the b"\\0" terminator.  All
+        requests are parsed first and draw their seeds from torch's global generator in list order.  Where the model refuses batch rows
+        (module docstring) the requests are served one after the other through the model's generate_stream, in the same (index, message)
+        shape."""
+        from medplib_amd.model.generation import StreamRequest
+        requests = [self._request(p) for p in params_list]
+        if self.model.model.llm.batch_rows_unsupported() is not None:
+            for index, rq in enumerate(requests):
+                for message in self._stream_one(rq):
+                    yield index, message
+            return
+        rows = max(1, min(8, int(self.args.limit_model_concurrency)))
+        for g0 in range(0, len(requests), rows):
+            group = requests[g0:g0 + rows]
+            batch = [StreamRequest(input_ids=rq.input_ids, images_clip=rq.clip, images=rq.sam, resize_list=rq.resize_list,
+                                   original_size_list=rq.original_size_list, region_masks=rq.region_masks,
+                                   valid_region_masks_bool=rq.region_valid, temperature=rq.temperature, top_p=rq.top_p, top_k=rq.top_k,
+                                   apply_top_p=rq.apply_top_p, max_new_tokens=rq.max_new_tokens, stop_token_id=rq.stop_idx, sample_seed=rq.seed,
+                                   stop_check=rq.stop_seen) for rq in group]
+            for row, new_ids, stopped, pred_mask in self.model.generate_stream_batch(
+                    batch, stream_interval=self.args.stream_interval, eos_token_id=self.tokenizer.eos_token_id):
+                yield g0 + row, self._message(group[row], new_ids, pred_mask)
 
     def generate_stream_gate(self, params):
         yield from self.generate_stream(params)
+
+    def generate_stream_gate_batch(self, params_list):
+        yield from self.generate_stream_batch(params_list)
