@@ -588,6 +588,26 @@ int mp_moe_residual_mix_bf16(const void* x, const void* moe, const void* mlp, co
 int mp_moe_route_top2(const float* gates, const float* logits, const float* noise, int tokens, int n_experts, int capacity,
                       int* expert, int* slot, float* weight, int* kept_counts, long long* exp_counts, float* l_aux,
                       hipStream_t stream);
+/* mp_moe_route_top1 / mp_moe_route_top2 for the right-padded prompts of ONE batched prefill, each prompt routed as a pass of its own
+ * (DeepSpeed's capacity and first-come drops are defined over the tokens of one pass: batch-mates and pad rows must not take a prompt's
+ * expert slots).  gates (top-2: and logits) fp32 [n_segments * seg_stride, n_experts]; segment b owns tokens b * seg_stride + i,
+ * i < seg_len[b], the rest of its stride is padding that is never read.  seg_len / seg_capacity [n_segments] are HOST arrays read at
+ * call time; there are no draw operands.  Per segment, expert, weight, the dropped set (slot < 0) and l_aux[b] are the bits of the
+ * unsegmented entry point on that segment's rows alone (tokens = seg_len[b], capacity = seg_capacity[b], null draws); a kept entry's slot
+ * is that call's slot plus the entries kept for the same expert in the segments before b, so an expert's kept rows are compact and
+ * segment-major in a slab of slab_rows rows (>= sum_b min(seg_capacity[b], seg_len[b] * top_k); the host passes sum_b seg_capacity[b]).
+ * expert / slot / weight: [T] (top-2: [2T], first choices at [0, T), second at [T, 2T)), T = n_segments * seg_stride; pad entries are
+ * stored as (0, -1, 0) and count nowhere.  kept_counts / exp_counts [n_experts]: summed over the segments; l_aux [n_segments];
+ * slot_token (top-1, optional) [n_experts * slab_rows]: global token index per slot; seg_kept / seg_exp_counts [n_segments * n_experts]:
+ * the segments' own counts (the first launch leaves them, the second reads them).  1 <= n_segments <= 8, 1 <= seg_len[b] <= seg_stride,
+ * else MP_ERR_SHAPE; a null operand is MP_ERR_ARG. */
+int mp_moe_route_top1_segments(const float* gates, const int* seg_len, const int* seg_capacity, int n_segments, int seg_stride,
+                               int n_experts, int slab_rows, int* expert, int* slot, float* weight, int* kept_counts,
+                               long long* exp_counts, float* l_aux, int* slot_token, int* seg_kept, long long* seg_exp_counts,
+                               hipStream_t stream);
+int mp_moe_route_top2_segments(const float* gates, const float* logits, const int* seg_len, const int* seg_capacity, int n_segments,
+                               int seg_stride, int n_experts, int slab_rows, int* expert, int* slot, float* weight, int* kept_counts,
+                               long long* exp_counts, float* l_aux, int* seg_kept, long long* seg_exp_counts, hipStream_t stream);
 /* Stateless draws for the gate: U(0,1) (RTS, top1gating) or Gumbel(0,1) (gumbel != 0; top2gating second-expert sampling)
  * from a hash of (seed, offset + i).  DeepSpeed uses torch's generator for these: same distribution, different stream. */
 int mp_gate_noise_f32(float* out, int64_t n, uint64_t seed, uint64_t offset, int gumbel, hipStream_t stream);

@@ -187,12 +187,14 @@ __global__ __launch_bounds__(512) void rmsnorm_gate_kernel(const bf16_t* __restr
 // uniform draws (DeepSpeed RTS; first-come when no draws are supplied); slot[s] = rank among KEPT tokens of that expert
 // in token order (cumsum(mask1) - 1), -1 if dropped; weight[s] = gates[s, expert] (not renormalised).
 // l_aux = E * sum_e mean_s(gates[:,e]) * mean_s(mask1[:,e])   (computed BEFORE dropping).
+// The body is a device function over the token range [0, T) of the pointers it is given, run by ONE 1024-thread workgroup: the kernel
+// below hands it a whole pass, moe_route_top1_segments_kernel one segment of a padded batch per workgroup.
 template <bool FAST>      // FAST: T <= 16 * 1024 -- a thread keeps its chunk's choices in registers (no second trip through global memory)
-__global__ __launch_bounds__(1024) void moe_route_top1_kernel(const float* __restrict__ gates, const float* __restrict__ rts, int T,
-                                                              int E, int capacity, int* __restrict__ expert, int* __restrict__ slot,
-                                                              float* __restrict__ weight, int* __restrict__ kept_counts,
-                                                              long long* __restrict__ exp_counts, float* __restrict__ l_aux,
-                                                              int* __restrict__ slot_token) {
+__device__ __forceinline__ void moe_route_top1_body(const float* __restrict__ gates, const float* __restrict__ rts, int T,
+                                                    int E, int capacity, int* __restrict__ expert, int* __restrict__ slot,
+                                                    float* __restrict__ weight, int* __restrict__ kept_counts,
+                                                    long long* __restrict__ exp_counts, float* __restrict__ l_aux,
+                                                    int* __restrict__ slot_token) {
   __shared__ float red[16];
   __shared__ int cnt_sh[MAXE];
   __shared__ int scan[16][MAXE];     // per-wave kept totals
@@ -470,6 +472,15 @@ __global__ __launch_bounds__(1024) void moe_route_top1_kernel(const float* __res
   }
   if (tid == 1023)
     for (int e = 0; e < E; ++e) kept_counts[e] = min(base[e], capacity);
+}
+
+template <bool FAST>
+__global__ __launch_bounds__(1024) void moe_route_top1_kernel(const float* __restrict__ gates, const float* __restrict__ rts, int T,
+                                                              int E, int capacity, int* __restrict__ expert, int* __restrict__ slot,
+                                                              float* __restrict__ weight, int* __restrict__ kept_counts,
+                                                              long long* __restrict__ exp_counts, float* __restrict__ l_aux,
+                                                              int* __restrict__ slot_token) {
+  moe_route_top1_body<FAST>(gates, rts, T, E, capacity, expert, slot, weight, kept_counts, exp_counts, l_aux, slot_token);
 }
 
 // ---------------- top-1 routing for a handful of tokens (T <= 64: the decode steps): one wave, lane = token ----------------
@@ -819,11 +830,13 @@ __global__ void moe_fill_dropped_kernel(const bf16_t* __restrict__ x, const int*
 // l_aux = E^2 * mean_e(mean_s gates * mean_s mask1); exp_counts = sum(mask1 + mask2) before dropping; a choice is dropped when
 // its location >= capacity (first-come by token position); the two surviving gate values are renormalised to sum to 1
 // (denominator clamped at fp32 eps).  Entry layout: first choices at [0, T), second choices at [T, 2T).
-__global__ __launch_bounds__(1024) void moe_route_top2_kernel(const float* __restrict__ gates, const float* __restrict__ logits,
-                                                              const float* __restrict__ noise, int T, int E, int capacity,
-                                                              int* __restrict__ expert, int* __restrict__ slot, float* __restrict__ weight,
-                                                              int* __restrict__ kept_counts, long long* __restrict__ exp_counts,
-                                                              float* __restrict__ l_aux) {
+// The body is a device function over the token range [0, T) of the pointers it is given, run by ONE 1024-thread workgroup; T2 is the
+// distance from a token's first-choice entry to its second-choice entry (T for a whole pass; the padded batch's token count for a segment).
+__device__ __forceinline__ void moe_route_top2_body(const float* __restrict__ gates, const float* __restrict__ logits,
+                                                    const float* __restrict__ noise, int T, int T2, int E, int capacity,
+                                                    int* __restrict__ expert, int* __restrict__ slot, float* __restrict__ weight,
+                                                    int* __restrict__ kept_counts, long long* __restrict__ exp_counts,
+                                                    float* __restrict__ l_aux) {
   __shared__ float red[16];
   __shared__ int tot1[MAXE], tot2[MAXE];
   __shared__ int scan1[16][MAXE], scan2[16][MAXE];
@@ -855,7 +868,7 @@ __global__ __launch_bounds__(1024) void moe_route_top2_kernel(const float* __res
       if (b2 < 0 || v > b2v) { b2v = v; b2 = e; }
     }
     if (b2 < 0) b2 = b1;                       // E == 1: degenerate, second choice dropped below
-    expert[s] = b1; expert[T + s] = b2;
+    expert[s] = b1; expert[T2 + s] = b2;
 #pragma unroll
     for (int k = 0; k < MAXE; ++k) { if (k == b1) c1[k] += 1; if (k == b2 && E > 1) c2[k] += 1; }
   }
@@ -902,7 +915,7 @@ __global__ __launch_bounds__(1024) void moe_route_top2_kernel(const float* __res
       base2[e] += tot1[e];                    // second choices sit behind ALL first choices of that expert
     }
   for (int s = s0; s < s1; ++s) {
-    const int e1 = expert[s], e2 = expert[T + s];
+    const int e1 = expert[s], e2 = expert[T2 + s];
     int l1 = 0, l2 = 0;
 #pragma unroll
     for (int k = 0; k < MAXE; ++k) {
@@ -913,9 +926,91 @@ __global__ __launch_bounds__(1024) void moe_route_top2_kernel(const float* __res
     float g1 = k1 ? gates[(int64_t)s * E + e1] : 0.f;
     float g2 = k2 ? gates[(int64_t)s * E + e2] : 0.f;
     const float den = fmaxf(g1 + g2, 1.1920929e-07f);
-    slot[s] = k1 ? l1 : -1; slot[T + s] = k2 ? l2 : -1;
-    weight[s] = g1 / den; weight[T + s] = g2 / den;
+    slot[s] = k1 ? l1 : -1; slot[T2 + s] = k2 ? l2 : -1;
+    weight[s] = g1 / den; weight[T2 + s] = g2 / den;
   }
+}
+
+__global__ __launch_bounds__(1024) void moe_route_top2_kernel(const float* __restrict__ gates, const float* __restrict__ logits,
+                                                              const float* __restrict__ noise, int T, int E, int capacity,
+                                                              int* __restrict__ expert, int* __restrict__ slot, float* __restrict__ weight,
+                                                              int* __restrict__ kept_counts, long long* __restrict__ exp_counts,
+                                                              float* __restrict__ l_aux) {
+  moe_route_top2_body(gates, logits, noise, T, T, E, capacity, expert, slot, weight, kept_counts, exp_counts, l_aux);
+}
+
+// ---------------- segmented routing: the right-padded prompts of one batched prefill, each routed as a pass of its own ----------------
+// Segment b owns tokens b * seg_stride + i, i < len[b]; the rest of its stride is padding that is never read.  DeepSpeed's capacity and its
+// first-come drops are defined over the tokens of one pass, so every segment gets its own capacity and its own cumsum: workgroup b runs the
+// body mp_moe_route_top1 / mp_moe_route_top2 would run on that segment alone (the same one of the three top-1 forms, chosen by len[b]), which
+// makes expert, weight, the dropped set and l_aux[b] those calls' bits by construction, and leaves the segment's own slots and counts
+// (seg_kept / seg_exp [n_segments, E]).  A second launch then shifts every kept slot behind the rows that earlier segments keep for the same
+// expert -- each expert's rows end up compact and segment-major in a slab of slab_rows rows -- fills slot_token, stores the pad entries and
+// sums the counts.  No workgroup waits for another one: the order between the two steps is the stream's.
+constexpr int MAXSEG = 8;
+struct RouteSegments {
+  int n, stride;
+  int len[MAXSEG], cap[MAXSEG];
+};
+
+__global__ __launch_bounds__(1024) void moe_route_top1_segments_kernel(const float* __restrict__ gates, RouteSegments seg, int E,
+                                                                       int* __restrict__ expert, int* __restrict__ slot,
+                                                                       float* __restrict__ weight, int* __restrict__ seg_kept,
+                                                                       long long* __restrict__ seg_exp, float* __restrict__ l_aux) {
+  const int b = blockIdx.x;
+  const int T = seg.len[b], cap = seg.cap[b];
+  const int64_t t0 = (int64_t)b * seg.stride;
+  gates += t0 * E; expert += t0; slot += t0; weight += t0;
+  seg_kept += b * E; seg_exp += b * E; l_aux += b;
+  if (T <= 64) {                       // (block-uniform, like the two branches below: mp_moe_route_top1's own choice of form)
+    if (threadIdx.x < 64)
+      moe_route_top1_small_body(gates, nullptr, T, E, cap, expert, slot, weight, seg_kept, seg_exp, l_aux, nullptr, threadIdx.x);
+  } else if (T <= 16 * 1024) {
+    moe_route_top1_body<true>(gates, nullptr, T, E, cap, expert, slot, weight, seg_kept, seg_exp, l_aux, nullptr);
+  } else {
+    moe_route_top1_body<false>(gates, nullptr, T, E, cap, expert, slot, weight, seg_kept, seg_exp, l_aux, nullptr);
+  }
+}
+
+__global__ __launch_bounds__(1024) void moe_route_top2_segments_kernel(const float* __restrict__ gates, const float* __restrict__ logits,
+                                                                       RouteSegments seg, int E, int* __restrict__ expert,
+                                                                       int* __restrict__ slot, float* __restrict__ weight,
+                                                                       int* __restrict__ seg_kept, long long* __restrict__ seg_exp,
+                                                                       float* __restrict__ l_aux) {
+  const int b = blockIdx.x;
+  const int64_t t0 = (int64_t)b * seg.stride;
+  moe_route_top2_body(gates + t0 * E, logits + t0 * E, nullptr, seg.len[b], seg.n * seg.stride, E, seg.cap[b], expert + t0, slot + t0,
+                      weight + t0, seg_kept + b * E, seg_exp + b * E, l_aux + b);
+}
+
+// One thread per entry (top-2: first choices at [0, T), second choices at [T, 2T), T = n * stride).
+__global__ __launch_bounds__(256) void moe_route_segments_finish_kernel(RouteSegments seg, int E, int top_k, int slab_rows,
+                                                                        int* __restrict__ expert, int* __restrict__ slot,
+                                                                        float* __restrict__ weight, const int* __restrict__ seg_kept,
+                                                                        const long long* __restrict__ seg_exp, int* __restrict__ kept_counts,
+                                                                        long long* __restrict__ exp_counts, int* __restrict__ slot_token) {
+  const int T = seg.n * seg.stride;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx < E) {
+    int kept = 0;
+    long long cnt = 0;
+    for (int b = 0; b < seg.n; ++b) { kept += seg_kept[b * E + idx]; cnt += seg_exp[b * E + idx]; }
+    kept_counts[idx] = kept; exp_counts[idx] = cnt;
+  }
+  if (idx >= top_k * T) return;
+  const int t = idx < T ? idx : idx - T;
+  const int b = t / seg.stride;
+  if (t - b * seg.stride >= seg.len[b]) {                     // padding: routed nowhere, counted nowhere
+    expert[idx] = 0; slot[idx] = -1; weight[idx] = 0.f;
+    return;
+  }
+  const int s = slot[idx];
+  if (s < 0) return;
+  const int e = expert[idx];
+  int base = 0;
+  for (int p = 0; p < b; ++p) base += seg_kept[p * E + e];
+  slot[idx] = base + s;
+  if (slot_token && base + s < slab_rows) slot_token[(int64_t)e * slab_rows + base + s] = t;
 }
 
 // ---------------- counter-based random draws for the gate (RTS uniforms, top-2 Gumbel noise) ----------------
@@ -1088,6 +1183,66 @@ extern "C" int mp_moe_route_top2(const float* gates, const float* logits, const 
   hipLaunchKernelGGL(moe_route_top2_kernel, dim3(1), dim3(1024), 0, stream, gates, logits, noise, tokens, n_experts, capacity, expert,
                      slot, weight, kept_counts, exp_counts, l_aux);
   return mp_check_launch("mp_moe_route_top2");
+}
+
+// The host-side limits of the two segmented entry points -> the kernels' argument block (seg_len / seg_capacity are HOST arrays).
+static int route_segments_args(const char* who, const int* seg_len, const int* seg_capacity, int n_segments, int seg_stride, int n_experts,
+                               int top_k, int slab_rows, RouteSegments* seg) {
+  MP_REQUIRE(seg_len != nullptr && seg_capacity != nullptr, MP_ERR_ARG, "%s: null operand", who);
+  MP_REQUIRE(n_segments >= 1 && n_segments <= MAXSEG && n_experts >= 1 && n_experts <= MAXE && seg_stride >= 1 &&
+                 (int64_t)n_segments * seg_stride * top_k <= INT32_MAX,
+             MP_ERR_SHAPE, "%s: 1..%d segments, experts <= %d (segments=%d stride=%d experts=%d)", who, MAXSEG, MAXE, n_segments, seg_stride,
+             n_experts);
+  int64_t rows = 0;
+  seg->n = n_segments; seg->stride = seg_stride;
+  for (int b = 0; b < MAXSEG; ++b) {
+    seg->len[b] = 0; seg->cap[b] = 0;
+    if (b >= n_segments) continue;
+    MP_REQUIRE(seg_len[b] >= 1 && seg_len[b] <= seg_stride && seg_capacity[b] >= 0, MP_ERR_SHAPE,
+               "%s: segment %d holds %d tokens of a stride of %d at capacity %d", who, b, seg_len[b], seg_stride, seg_capacity[b]);
+    seg->len[b] = seg_len[b]; seg->cap[b] = seg_capacity[b];
+    const int64_t entries = (int64_t)seg_len[b] * top_k;
+    rows += seg_capacity[b] < entries ? seg_capacity[b] : entries;
+  }
+  MP_REQUIRE(slab_rows >= rows, MP_ERR_SHAPE, "%s: slab_rows=%d cannot hold the %lld rows the segments may keep for one expert", who, slab_rows,
+             (long long)rows);
+  return MP_OK;
+}
+
+extern "C" int mp_moe_route_top1_segments(const float* gates, const int* seg_len, const int* seg_capacity, int n_segments, int seg_stride,
+                                          int n_experts, int slab_rows, int* expert, int* slot, float* weight, int* kept_counts,
+                                          long long* exp_counts, float* l_aux, int* slot_token, int* seg_kept, long long* seg_exp_counts,
+                                          hipStream_t stream) {
+  RouteSegments seg;
+  const int rc = route_segments_args("mp_moe_route_top1_segments", seg_len, seg_capacity, n_segments, seg_stride, n_experts, 1, slab_rows, &seg);
+  if (rc != MP_OK) return rc;
+  MP_REQUIRE(gates && expert && slot && weight && kept_counts && exp_counts && l_aux && seg_kept && seg_exp_counts, MP_ERR_ARG,
+             "mp_moe_route_top1_segments: null operand");
+  hipLaunchKernelGGL(moe_route_top1_segments_kernel, dim3(n_segments), dim3(1024), 0, stream, gates, seg, n_experts, expert, slot, weight,
+                     seg_kept, seg_exp_counts, l_aux);
+  const int rc1 = mp_check_launch("mp_moe_route_top1_segments");
+  if (rc1 != MP_OK) return rc1;
+  hipLaunchKernelGGL(moe_route_segments_finish_kernel, dim3((unsigned)mp_cdiv((int64_t)n_segments * seg_stride, 256)), dim3(256), 0, stream, seg,
+                     n_experts, 1, slab_rows, expert, slot, weight, seg_kept, seg_exp_counts, kept_counts, exp_counts, slot_token);
+  return mp_check_launch("mp_moe_route_top1_segments(finish)");
+}
+
+extern "C" int mp_moe_route_top2_segments(const float* gates, const float* logits, const int* seg_len, const int* seg_capacity, int n_segments,
+                                          int seg_stride, int n_experts, int slab_rows, int* expert, int* slot, float* weight,
+                                          int* kept_counts, long long* exp_counts, float* l_aux, int* seg_kept, long long* seg_exp_counts,
+                                          hipStream_t stream) {
+  RouteSegments seg;
+  const int rc = route_segments_args("mp_moe_route_top2_segments", seg_len, seg_capacity, n_segments, seg_stride, n_experts, 2, slab_rows, &seg);
+  if (rc != MP_OK) return rc;
+  MP_REQUIRE(gates && logits && expert && slot && weight && kept_counts && exp_counts && l_aux && seg_kept && seg_exp_counts, MP_ERR_ARG,
+             "mp_moe_route_top2_segments: null operand");
+  hipLaunchKernelGGL(moe_route_top2_segments_kernel, dim3(n_segments), dim3(1024), 0, stream, gates, logits, seg, n_experts, expert, slot,
+                     weight, seg_kept, seg_exp_counts, l_aux);
+  const int rc1 = mp_check_launch("mp_moe_route_top2_segments");
+  if (rc1 != MP_OK) return rc1;
+  hipLaunchKernelGGL(moe_route_segments_finish_kernel, dim3((unsigned)mp_cdiv((int64_t)n_segments * seg_stride * 2, 256)), dim3(256), 0, stream,
+                     seg, n_experts, 2, slab_rows, expert, slot, weight, seg_kept, seg_exp_counts, kept_counts, exp_counts, nullptr);
+  return mp_check_launch("mp_moe_route_top2_segments(finish)");
 }
 
 extern "C" int mp_gate_noise_f32(float* out, int64_t n, uint64_t seed, uint64_t offset, int gumbel, hipStream_t stream) {

@@ -39,6 +39,8 @@ def parse_args(argv=None):
     p.add_argument("--answers_file", default="")
     p.add_argument("--decode_batch", default=1, type=int,
                    help="--eval_vqa: samples decoded together per generate_batch() call (1..8); 1 = one generate() call per sample")
+    p.add_argument("--prefill_batch", action="store_true", default=False,
+                   help="--eval_vqa with --decode_batch > 1: the prompts of a group are prefilled as one padded pass (generate_batch(batch_prefill=True))")
     p.add_argument("--colon_token_id", default=COLON_ID, type=int)
     # the model flags build_model reads (train.py)
     for name, typ, dv in (("moe_enable", lambda s: s.lower() in ("1", "true"), True), ("num_experts", int, 2), ("top_k_experts", int, 1),
@@ -92,9 +94,10 @@ def validate_seg(val, model, device, max_new_tokens=64, colon_id=COLON_ID):
 
 
 @torch.no_grad()
-def _generate_together(model, samples, cuts, max_new_tokens, eos=2):
+def _generate_together(model, samples, cuts, max_new_tokens, eos=2, prefill_batch=False):
     """The single-sample batches `samples` (prompts cut at `cuts`) through ONE generate_batch() call -> per sample the ids [1, cut + n] that
-    generate() returns for it alone (its own padding removed).  eos: generate()'s default stop id, which the VQA loop decodes with."""
+    generate() returns for it alone (its own padding removed).  eos: generate()'s default stop id, which the VQA loop decodes with.
+    prefill_batch: generate_batch()'s batch_prefill."""
     for b in samples:
         if any(b.get(k) is not None for k in ("mask_images", "image_token_types", "image_token_lengths")):
             raise NotImplementedError("--decode_batch > 1 with in-context mask images (mask_images / image_token_types / image_token_lengths) "
@@ -110,7 +113,8 @@ def _generate_together(model, samples, cuts, max_new_tokens, eos=2):
     regions = [m for b in samples for m in (b.get("region_masks") or ())]
     valid = [v for b in samples for v in (b.get("valid_region_masks_bool") or ())]
     out = model.generate_batch(ids, images=images, attention_mask=att, max_new_tokens=max_new_tokens, eos_token_id=eos,
-                               batch_rows=len(samples), region_masks=regions or None, valid_region_masks_bool=valid or None)
+                               batch_rows=len(samples), batch_prefill=prefill_batch, region_masks=regions or None,
+                               valid_region_masks_bool=valid or None)
     rows = []
     for r, cut in enumerate(cuts):
         n_prompt = int(att[r].sum())
@@ -123,14 +127,18 @@ def _generate_together(model, samples, cuts, max_new_tokens, eos=2):
 
 
 @torch.no_grad()
-def run_vqa(val, model, device, max_new_tokens=64, colon_id=COLON_ID, answers_file="", tokenizer=None, decode_batch=1):
+def run_vqa(val, model, device, max_new_tokens=64, colon_id=COLON_ID, answers_file="", tokenizer=None, decode_batch=1,
+            prefill_batch=False):
     """-> list of generated id tensors (prompt + continuation, as HF `generate` returns them).  With `answers_file`: one JSON line
     per sample {question_id, image_path, prompt, text | output_ids, gt} (vqa_infer.py:470-480); `text` needs a tokenizer with
     `batch_decode`, otherwise the new ids are written.  decode_batch > 1: that many samples are collected per generate_batch() call (their
-    prompts are the rows of one decode step); the answers file has the same records in the same order."""
+    prompts are the rows of one decode step); the answers file has the same records in the same order.  prefill_batch (needs
+    decode_batch > 1): every group's prompts are prefilled as one padded pass (generate_batch(batch_prefill=True))."""
     model.eval()
     if not 1 <= int(decode_batch) <= 8:
         raise ValueError(f"--decode_batch {decode_batch} must lie in 1..8")
+    if prefill_batch and decode_batch <= 1:
+        raise ValueError("--prefill_batch needs --decode_batch > 1 (the prompts of a generate_batch() group share the prefill pass)")
     outs = []
     fh = None
     if answers_file:
@@ -144,7 +152,7 @@ def run_vqa(val, model, device, max_new_tokens=64, colon_id=COLON_ID, answers_fi
             if i not in ready:
                 group = [b] + [dict_to_device(val[j], device) for j in range(i + 1, min(i + decode_batch, len(val)))]
                 cuts = [prompt_cut(s["input_ids"], colon_id) for s in group]
-                ready = dict(zip(range(i, i + len(group)), _generate_together(model, group, cuts, max_new_tokens)))
+                ready = dict(zip(range(i, i + len(group)), _generate_together(model, group, cuts, max_new_tokens, prefill_batch=prefill_batch)))
             out = ready[i]
         else:
             out = model.generate(b["input_ids"][:, :cut], images=b["images_clip"], attention_mask=b["attention_mask"][:, :cut],
@@ -180,7 +188,7 @@ def main(argv=None):
     out = {}
     if args.eval_vqa:
         out["vqa_output_ids"] = run_vqa(val, model, device, args.max_new_tokens, args.colon_token_id, args.answers_file,
-                                        getattr(val, "tokenizer", None), decode_batch=args.decode_batch)
+                                        getattr(val, "tokenizer", None), decode_batch=args.decode_batch, prefill_batch=args.prefill_batch)
     if args.eval_seg:
         out["miou"], out["mdice"], out["per_modality"] = validate_seg(val, model, device, args.max_new_tokens, args.colon_token_id)
     return out

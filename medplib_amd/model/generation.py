@@ -639,14 +639,25 @@ class GenerationMixin:
         S = plan.seq_len
         return ops.splice_rows(llm.embed_tokens, feats, src, cfg.hidden_size).view(1, S, cfg.hidden_size), S
 
-    def _prefill_batch(self, prompts, max_new_tokens):
+    def _prefill_batch(self, prompts, max_new_tokens, batched=False):
         """The prompts of a batch group — (ids, images_clip, extras) each — planned first, then each prefilled at batch 1 (the bits of
         generate()'s prefill) into its own row of ONE KV cache of len(prompts) rows and max(S_b) + max_new_tokens positions, allocated before
-        the first prefill so that the RoPE tables have grown before anything is captured.  -> ([hidden per row], cache, [S_b])."""
+        the first prefill so that the RoPE tables have grown before anything is captured.  -> ([hidden per row], cache, [S_b]).
+        batched: the planned embeddings stacked, zero-padded on the right to max(S_b), through ONE LlamaStack.forward(seg_lens=[S_b]) into
+        the group's cache — one pass over the weights for the group, every MoE layer routing each prompt as a pass of its own; the hidden
+        states per row are views [1, S_b, d] of that pass's output.  The K/V the pad positions wrote are dead by construction: row b's first
+        decode step appends at S_b, over the first of them, and the key count per row bounds every read, so no step ever reads a pad
+        position's K/V.  A group of one takes the per-row path either way (the same launches)."""
         llm = self.model.llm
         planned = [self._plan_embeds(*p) for p in prompts]
         lengths = [S for _, S in planned]
         cache = llm.new_kv_cache(len(prompts), max(lengths) + max_new_tokens)
+        if batched and len(prompts) > 1:
+            embeds = torch.zeros((len(prompts), max(lengths), self.config.hidden_size), dtype=planned[0][0].dtype, device=self.device_)
+            for b, (row, S) in enumerate(planned):
+                embeds[b, :S].copy_(row[0])
+            hidden = llm.forward(embeds, None, kv_cache=cache, seg_lens=lengths)[0]
+            return [hidden[b:b + 1, :S] for b, S in enumerate(lengths)], cache, lengths
         hiddens = []
         for b, (embeds, S) in enumerate(planned):
             row = {"len": 0, "k": [t[b:b + 1] for t in cache["k"]], "v": [t[b:b + 1] for t in cache["v"]], "err": cache["err"]}
@@ -690,13 +701,15 @@ class GenerationMixin:
         policy = _single_row_policy(self.model.llm, hidden, cache, max_new_tokens, stop_ids, pick, debug, captured)
         yield from self._drive(policy, hidden, cache, S, max_new_tokens, captured, looks)
 
-    def _decode_batch(self, prompts, max_new_tokens, stop_ids, pick=_argmax_pick, looks=None, debug=None, row_limits=None, row_stop_ids=None):
+    def _decode_batch(self, prompts, max_new_tokens, stop_ids, pick=_argmax_pick, looks=None, debug=None, row_limits=None, row_stop_ids=None,
+                      batch_prefill=False):
         """_decode for the prompts of one batch group, (ids, images_clip, extras) each, as the rows of one decode step (_batch_policy): every
         prompt prefilled at batch 1 into its row of one cache, then single-token steps at B rows with a position and a key count per row,
         the next tokens chosen by `pick` over the [B, V] logits.  Through the captured graph under _decode's conditions, else token by token.
         A generator of ([generated ids so far per row], [stopped per row], [[hidden states of the prompt, of each fed token] per row]).
-        row_limits / row_stop_ids: a max_new_tokens and a stop-id set per row (_batch_policy)."""
-        hiddens, cache, lengths = self._prefill_batch(prompts, max_new_tokens)
+        row_limits / row_stop_ids: a max_new_tokens and a stop-id set per row (_batch_policy).  batch_prefill: the group's prompts through one
+        padded pass instead of a prefill per row (_prefill_batch(batched=True))."""
+        hiddens, cache, lengths = self._prefill_batch(prompts, max_new_tokens, batched=batch_prefill)
         captured = self._captures(max_new_tokens)
         policy = _batch_policy(self.model.llm, hiddens, cache, lengths, max_new_tokens, stop_ids, pick, debug, captured, row_limits, row_stop_ids)
         last = torch.cat([h[0, -1:] for h in hiddens])
@@ -745,7 +758,8 @@ class GenerationMixin:
                                    lambda b, row, img, extras: self._greedy(row, img, max_new_tokens, eos_token_id, extras)[0])
 
     @torch.no_grad()
-    def generate_batch(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, batch_rows=8, **kwargs):
+    def generate_batch(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, batch_rows=8, batch_prefill=False,
+                       **kwargs):
         """generate() with the prompts decoded TOGETHER: the rows are taken in groups of `batch_rows` (1..8, else ValueError) and the prompts
         of a group — whatever their lengths — are the rows of one decode step, so a group pays one pass over the decoder weights per token
         instead of one per prompt (_decode_batch, _batch_policy).  Each prompt is prefilled at batch 1 as in generate(); a row stops at its
@@ -759,8 +773,13 @@ class GenerationMixin:
         included, right-padded with eos.  batch_rows = 8: the shared GEMV reads the weights once for up to four rows and twice for five to
         eight, and eight rows still gave more tokens per second than four on the dense and on the MoE model at 7B (profiles/batch_decode.md:
         +10 % and +13 %; four rows are the better latency).  Refused: sampling (generate_sample) and beams (generate_beam) per row, and — NotImplementedError
-        before any state changes — gate sampling or an injected draw provider, the residual MoE and expert parallelism.  Not built: batched
-        prefill, evaluate() / <SEG> masks per batch."""
+        before any state changes — gate sampling or an injected draw provider, the residual MoE and expert parallelism.
+        batch_prefill=True (off by default): a group of two or more prompts is prefilled as ONE pass over the prompts right-padded to the
+        longest (_prefill_batch(batched=True), LlamaStack.forward(seg_lens=)) instead of one pass per prompt.  A MoE layer of that pass routes
+        every prompt as a pass of its own, at the capacity of its own length (ops.moe_route_top1_segments / _top2_segments): the experts, the
+        dropped tokens and the slot order of a prompt are those of its batch-1 prefill on the same gate values, whoever its batch-mates are.
+        The GEMMs see other row counts than at batch 1, so a row is the per-row prefill's function in another summation order, not its bits.
+        Not built: evaluate() / <SEG> masks per batch."""
         _check_kwargs("generate_batch", kwargs)
         n_rows, max_new_tokens = int(batch_rows), int(max_new_tokens)
         if not 1 <= n_rows <= 8:
@@ -769,14 +788,15 @@ class GenerationMixin:
         why = self.model.llm.batch_rows_unsupported()
         if why is not None:
             raise NotImplementedError(f"generate_batch(): {why}: call generate()")
-        return self._generate_groups(input_ids, images, attention_mask, max_new_tokens, eos_token_id, n_rows, kwargs, _argmax_pick)
+        return self._generate_groups(input_ids, images, attention_mask, max_new_tokens, eos_token_id, n_rows, kwargs, _argmax_pick,
+                                     batch_prefill=batch_prefill)
 
     @torch.no_grad()
     def _generate_groups(self, input_ids, images, attention_mask, max_new_tokens, eos_token_id, n_rows, kwargs, pick, pick_of_group=None,
-                         who="generate_batch", debug=None):
+                         who="generate_batch", debug=None, batch_prefill=False):
         """generate_batch() behind its argument checks: the rows in groups of n_rows through _decode_batch, the next tokens chosen by
         pick(logits [B, V], step) -> int64 [B] — or, with pick_of_group(first row, rows) -> pick, by a pick made for each group (the rows'
-        own sampling parameters); output ids [B, L + n_max], prompt included, right-padded with eos."""
+        own sampling parameters); output ids [B, L + n_max], prompt included, right-padded with eos.  batch_prefill: _decode_batch's."""
         ids = _np_ids(input_ids).astype(np.int64)
         rows = []
         with self._decoding(who):
@@ -787,7 +807,8 @@ class GenerationMixin:
                 if pick_of_group is not None:
                     pick = pick_of_group(g0, len(group))
                 # (closed before the prologue is undone: the driver's `finally` settles the pass counter)
-                with contextlib.closing(self._decode_batch(group, max_new_tokens, (eos_token_id,), pick=pick, debug=debug)) as steps:
+                with contextlib.closing(self._decode_batch(group, max_new_tokens, (eos_token_id,), pick=pick, debug=debug,
+                                                           batch_prefill=batch_prefill)) as steps:
                     for generated, _, _ in steps:
                         pass
                 rows += [np.concatenate([p[0][0], np.asarray(g, dtype=np.int64)]) for p, g in zip(group, generated)]
@@ -829,9 +850,10 @@ class GenerationMixin:
         exact: token i of row b is the single-row op (ops.sample_rows / ops.sample_rows_filtered, by generate_sample()'s rule) on that step's
         own logits row at the draw for (sample_seed + b, i).  ValueError for a temperature that is not > 0 and for do_sample=False;
         NotImplementedError, before any state changes, for beams and wherever generate_batch() refuses the model (gate sampling or an
-        injected draw provider, the residual MoE, expert parallelism).  debug: a list that receives (fp32 logits [B, V], u [B], tokens [B])
+        injected draw provider, the residual MoE, expert parallelism).  batch_prefill=True (a keyword, off by default): generate_batch()'s
+        switch, one padded prefill pass per group.  debug: a list that receives (fp32 logits [B, V], u [B], tokens [B])
         per kept step of every group (tests; costs a sync per token)."""
-        debug = kwargs.pop("debug", None)
+        debug, batch_prefill = kwargs.pop("debug", None), bool(kwargs.pop("batch_prefill", False))
         n_prompts = int(_np_ids(input_ids).shape[0])
 
         def per_row(value, name, cast):
@@ -864,7 +886,7 @@ class GenerationMixin:
             return _RowsPick(temperatures[rows], top_ks[rows], top_ps[rows], [seed + b for b in range(g0, g0 + n)], self.device_)
 
         return self._generate_groups(input_ids, images, attention_mask, max_new_tokens, eos_token_id, n_rows, kwargs, None,
-                                     pick_of_group=pick_of_group, who="generate_sample_batch", debug=debug)
+                                     pick_of_group=pick_of_group, who="generate_sample_batch", debug=debug, batch_prefill=batch_prefill)
 
     @torch.no_grad()
     def generate_beam(self, input_ids, images=None, attention_mask=None, max_new_tokens=512, eos_token_id=2, num_beams=4, length_penalty=1.0,
@@ -970,7 +992,9 @@ class GenerationMixin:
         Decode path (last_decode_path): the captured graph under generate_batch()'s conditions, else the loop; the host looks at the ids every
         stream_interval steps (and at the rows' last tokens).  A row is generate_stream()'s function in another summation order; exact is what
         generate_sample_batch() states: every token is the single-row op on its step's own logits row at the draw for (sample_seed, i).
-        `uniforms` injection is not offered.  NotImplementedError, before any state changes, wherever generate_batch() refuses the model.
+        `uniforms` injection is not offered.  self.stream_batch_prefill = True (an attribute of the model beside decode_with_graph, off by
+        default; this method's arguments are the worker's) is generate_batch()'s batch_prefill for the groups served here: one padded prefill
+        pass for the group, so the time to the group's first token is one pass, not the sum of the rows' prefills.  NotImplementedError, before any state changes, wherever generate_batch() refuses the model.
         debug: a list that receives (fp32 logits [B, V], u [B], tokens [B]) per kept step (tests; costs a sync per token)."""
         requests = list(requests)
         if not 1 <= len(requests) <= 8:
@@ -986,10 +1010,10 @@ class GenerationMixin:
                          [int(r.top_k or 0) if f else 0 for r, f in zip(requests, filtered)],
                          [(1.0 if r.top_p is None else float(r.top_p)) if f else 1.0 for r, f in zip(requests, filtered)],
                          [r.sample_seed for r in requests], self.device_)
-        return self._stream_batch(requests, limits, pick, max(1, int(stream_interval)), eos_token_id, debug)
+        return self._stream_batch(requests, limits, pick, max(1, int(stream_interval)), eos_token_id, debug, bool(self.stream_batch_prefill))
 
     @torch.no_grad()
-    def _stream_batch(self, requests, limits, pick, every, eos_token_id, debug):
+    def _stream_batch(self, requests, limits, pick, every, eos_token_id, debug, batch_prefill=False):
         """generate_stream_batch() behind its argument checks."""
         with self._decoding("generate_stream_batch"):
             B, n_max = len(requests), max(limits)
@@ -1003,7 +1027,7 @@ class GenerationMixin:
             looks = sorted({i + 1 for i in range(n_max) if i % every == 0} | set(limits))
             finished, sent = [False] * B, [0] * B
             with contextlib.closing(self._decode_batch(prompts, n_max, (), pick=pick, looks=looks, debug=debug, row_limits=limits,
-                                                       row_stop_ids=stops)) as steps:
+                                                       row_stop_ids=stops, batch_prefill=batch_prefill)) as steps:
                 for generated, stopped_rows, hiddens in steps:
                     for b, r in enumerate(requests):
                         new = list(generated[b])

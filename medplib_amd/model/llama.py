@@ -310,10 +310,10 @@ class LlamaStack:
         act = ops.gemv_top2_gate_up(h, lw["gu"], expert, slot)
         return ops.gemv_top2_down(act, lw["down"], expert, slot, weight, x)
 
-    def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None, pass_dev=None, copies=None, cap=None):
+    def _mlp(self, i, lw, h, x, gate=None, needed=None, rstd=None, pass_dev=None, copies=None, cap=None, seg=None):
         """x + MLP(h): h = post-attention RMSNorm output [T,d], x = residual stream [T,d]; gate = (logits, gates) when the caller's fused
         norm kernel already produced them (ops.rmsnorm_gate); needed = (rows, mask) when only those output rows are read (the last layer);
-        rstd: the folded post-attention norm (h is None then); copies: the layer's quantised copies (_decode_copies) when the rows are decode rows; cap: the ragged rows of a batch (decode_step with `rows`) — that capacity (T: nothing dropped), no draws, the grouped expert GEMVs.  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
+        rstd: the folded post-attention norm (h is None then); copies: the layer's quantised copies (_decode_copies) when the rows are decode rows; cap: the ragged rows of a batch (decode_step with `rows`) — that capacity (T: nothing dropped), no draws, the grouped expert GEMVs; seg = (seg_lens, seg_stride, capacities): the rows are the right-padded prompts of a batched prefill (forward with seg_lens) — every prompt routed as a pass of its own (ops.moe_route_top1_segments / _top2_segments), never the expert-GEMV rows.  Selects the branch -> (out, l_aux, (expert, slot, counts)); None, None when dense."""
         cfg, T = self.cfg, x.shape[0]
         if i not in self.moe_layers:
             if T <= 8:
@@ -323,6 +323,10 @@ class LlamaStack:
         ragged = cap is not None
         E, k, cap = cfg.num_experts, cfg.top_k_experts, cap if ragged else self.capacity(T)
         logits, gates = gate if gate is not None else ops.moe_gate(h, lw["wg"])
+        if seg is not None:        # (forward refused expert parallelism and the residual MoE: batch_rows_unsupported)
+            if k == 1 and self.fuse_moe_gather_scatter:
+                return self._mlp_gather_scatter(i, lw, h, x, gates, None, None, None, None, seg=seg)
+            return self._mlp_dispatch_combine(i, lw, h, x, logits, gates, None, None, seg=seg)
         if k == 1 and self._expert_gemv_rows(T):
             # (no gate draws: random token selection only acts when an expert is over capacity; below cap >= T the draws are generated as usual)
             draws = None if cap >= T else self._gate_draws(i, T, E, False, pass_dev)
@@ -335,11 +339,17 @@ class LlamaStack:
             return self._mlp_gather_scatter(i, lw, h, x, gates, cap, needed, rstd, pass_dev)
         return self._mlp_dispatch_combine(i, lw, h, x, logits, gates, cap, pass_dev)
 
-    def _mlp_gather_scatter(self, i, lw, h, x, gates, cap, needed, rstd, pass_dev):
+    def _mlp_gather_scatter(self, i, lw, h, x, gates, cap, needed, rstd, pass_dev, seg=None):
         """Top-1 on one rank: the dispatch is a row gather in the gate|up GEMM's operand fetch and the combine (gate weight and the layer's
-        residual add) a row scatter in the down GEMM's epilogue; every routed token's row is written exactly once."""
+        residual add) a row scatter in the down GEMM's epilogue; every routed token's row is written exactly once.
+        seg (_mlp): the segmented routing's slot_token / kept pair over slabs of sum(capacities) rows; a pad row is routed nowhere and keeps
+        the residual stream, like a dropped token."""
         E, ff, T = self.cfg.num_experts, self.cfg.intermediate_size, x.shape[0]
-        expert, slot, weight, kept, counts, l_aux, slot_token = ops.moe_route_top1(gates, cap, self._gate_draws(i, T, E, False, pass_dev), want_slot_token=True)
+        if seg is not None:
+            cap = sum(seg[2])
+            expert, slot, weight, kept, counts, l_aux, slot_token = ops.moe_route_top1_segments(gates, *seg, want_slot_token=True)
+        else:
+            expert, slot, weight, kept, counts, l_aux, slot_token = ops.moe_route_top1(gates, cap, self._gate_draws(i, T, E, False, pass_dev), want_slot_token=True)
         act = torch.empty((E, cap, ff), dtype=torch.bfloat16, device=x.device)
         if needed is not None:
             self.pruned_rows = int(needed[0].numel())      # the pruning HAPPENED (model_forward reports only this)
@@ -361,11 +371,18 @@ class LlamaStack:
         ops.gemm_batched_rows(act, lw["down"], x, kept, c_rows=slot_token, c_scale=weight, residual=x, rows_stride=cap)
         return x, l_aux, (expert, slot, counts)
 
-    def _mlp_dispatch_combine(self, i, lw, h, x, logits, gates, cap, pass_dev):
-        """The generic MoE branch (top-2, unfused top-1, expert parallelism, residual MoE): dispatch into capacity slabs, batched expert GEMM pair, combine."""
+    def _mlp_dispatch_combine(self, i, lw, h, x, logits, gates, cap, pass_dev, seg=None):
+        """The generic MoE branch (top-2, unfused top-1, expert parallelism, residual MoE): dispatch into capacity slabs, batched expert GEMM pair, combine.
+        seg (_mlp): the segmented routing's entry arrays over slabs of sum(capacities) rows; a pad row's entries are dropped ones."""
         cfg = self.cfg
         E, ff, d, k, T = cfg.num_experts, cfg.intermediate_size, cfg.hidden_size, cfg.top_k_experts, x.shape[0]
-        if k == 1:
+        if seg is not None:
+            cap = sum(seg[2])
+            if k == 1:
+                expert, slot, weight, kept, counts, l_aux = ops.moe_route_top1_segments(gates, *seg)
+            else:
+                expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2_segments(gates, logits, *seg)
+        elif k == 1:
             expert, slot, weight, kept, counts, l_aux = ops.moe_route_top1(gates, cap, self._gate_draws(i, T, E, False, pass_dev))
         else:
             expert, slot, weight, kept, counts, l_aux = ops.moe_route_top2(gates, logits, cap, self._gate_draws(i, T, E, True, pass_dev))
@@ -469,14 +486,33 @@ class LlamaStack:
             return h, (lg, gt), None
         return ops.rmsnorm(x, lw["ln2"], cfg.rms_norm_eps), None, None
 
-    def forward(self, inputs_embeds, key_valid=None, collect_routing=False, kv_cache=None):
+    def forward(self, inputs_embeds, key_valid=None, collect_routing=False, kv_cache=None, seg_lens=None):
         """inputs_embeds [B,S,d] bf16; key_valid uint8 [B,S] (1 = real token) or None.
         With kv_cache: the S new tokens sit at positions cache.len .. cache.len+S-1, their K/V are appended and attention runs
         over the whole cache (prefill when cache.len == 0, single-token decode afterwards).
+        seg_lens (a list of B ints): the batched prefill of a decode group — row b is a prompt of seg_lens[b] positions, right-padded to S,
+        into an EMPTY kv_cache and without key_valid (right padding under the causal mask: no real query sees a pad key).  Everything but the
+        routing is the [B, S] pass; a MoE layer routes every prompt as a pass of its own, at capacity(seg_lens[b]) (ops.moe_route_top1_segments /
+        _top2_segments: no prompt loses an expert slot to a batch-mate or to padding), through the expert GEMMs whatever B * S is (never the
+        expert GEMVs of the decode rows, never the folded norms); the pad rows are routed nowhere and only carry the residual stream, and
+        what they leave in the hidden states and in the cache is for the caller to ignore.  One pass: gate_pass advances by one.
+        ValueError for a cache that is missing or not empty, key_valid, or a length outside 1..S; NotImplementedError where
+        batch_rows_unsupported() says so — both before any state changes.
         Returns (last_hidden_state after the final RMSNorm [B,S,d], [l_aux per MoE layer], routing or None)."""
         cfg = self.cfg
         B, S, d = inputs_embeds.shape
         H, D = cfg.num_attention_heads, cfg.head_dim
+        seg = None
+        if seg_lens is not None:
+            seg_lens = [int(n) for n in seg_lens]
+            if kv_cache is None or kv_cache["len"] != 0 or key_valid is not None:
+                raise ValueError("LlamaStack.forward: seg_lens is the batched prefill of a decode group: it needs an empty kv_cache and no key_valid")
+            if len(seg_lens) != B or not all(1 <= n <= S for n in seg_lens):
+                raise ValueError(f"LlamaStack.forward: seg_lens={seg_lens} must hold {B} lengths in 1..{S}")
+            why = self.batch_rows_unsupported()
+            if why is not None:
+                raise NotImplementedError(f"forward with seg_lens: {why}")
+            seg = (seg_lens, S, [self.capacity(n) for n in seg_lens])
         x = inputs_embeds.reshape(B * S, d)
         aux, routing, gate_inputs = [], [], []
         nr = self.needed_rows               # (rows, mask) from model_forward: the output rows something reads, or None
@@ -511,7 +547,7 @@ class LlamaStack:
             x_gate_in = x.clone() if (collect_routing and i in self.moe_layers) else None
             h, gate, rstd = self._post_attention_norm(i, lw, x, folded)
             # (the last layer's row set goes to _mlp whatever produced the gate: only the top-1 gather / scatter branch prunes, a dense layer ignores it)
-            x, l_aux, r = self._mlp(i, lw, h, x, gate=gate, needed=needed if i == last else None, rstd=rstd, copies=copies)
+            x, l_aux, r = self._mlp(i, lw, h, x, gate=gate, needed=needed if i == last else None, rstd=rstd, copies=copies, seg=seg)
             if l_aux is not None:
                 aux.append(l_aux)
                 if collect_routing:

@@ -156,6 +156,7 @@ class MedPLIBForCausalLM(GenerationMixin, nn.Module):
         # against the next tail by the tail stream itself.  Anything else that touches trainable state calls sync_side_streams().
         self.decode_with_graph = True            # evaluate(): replay one captured HIP graph per generated token
         self.last_decode_path = None             # "graph" or "loop": how the last generate() / evaluate() decoded
+        self.stream_batch_prefill = False        # generate_stream_batch(): the group's prompts through one padded prefill pass (generate_batch's batch_prefill)
         self._shadow_depth = 0                   # open adapters_merged() blocks (the decode entry points nest inside a caller's)
         self.tail_side_stream = False
         self._tail_stream_obj = None

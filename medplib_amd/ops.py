@@ -2001,6 +2001,42 @@ def moe_route_top2(gates, logits, capacity, noise=None):
     return expert, slot, weight, kept, counts, l_aux
 
 
+def _route_segments(name, top_k, gates, logits, seg_lens, seg_stride, caps, want_slot_token):
+    import ctypes
+    T, E = gates.shape
+    n = len(seg_lens)
+    assert len(caps) == n and T == n * int(seg_stride) and gates.is_contiguous() and (logits is None or logits.is_contiguous())
+    dev = gates.device
+    slab_rows = sum(int(c) for c in caps)
+    lens_c = (ctypes.c_int * n)(*[int(s) for s in seg_lens]); caps_c = (ctypes.c_int * n)(*[int(c) for c in caps])
+    expert = torch.empty(top_k * T, dtype=torch.int32, device=dev); slot = torch.empty(top_k * T, dtype=torch.int32, device=dev)
+    weight = torch.empty(top_k * T, dtype=torch.float32, device=dev)
+    kept = torch.empty(E, dtype=torch.int32, device=dev); counts = torch.empty(E, dtype=torch.int64, device=dev)
+    l_aux = torch.empty(n, dtype=torch.float32, device=dev)
+    seg_kept = torch.empty(n * E, dtype=torch.int32, device=dev); seg_counts = torch.empty(n * E, dtype=torch.int64, device=dev)      # the two launches' hand-over
+    slot_token = torch.empty((E, slab_rows), dtype=torch.int32, device=dev) if want_slot_token else None
+    head = (_p(gates),) if logits is None else (_p(gates), _p(logits))
+    tail = (_p(slot_token),) if top_k == 1 else ()
+    lib().call(name, *head, ctypes.cast(lens_c, ctypes.c_void_p), ctypes.cast(caps_c, ctypes.c_void_p), n, int(seg_stride), E, slab_rows,
+               _p(expert), _p(slot), _p(weight), _p(kept), _p(counts), _p(l_aux), *tail, _p(seg_kept), _p(seg_counts), _stream())
+    if want_slot_token:
+        return expert, slot, weight, kept, counts, l_aux, slot_token
+    return expert, slot, weight, kept, counts, l_aux
+
+
+def moe_route_top1_segments(gates, seg_lens, seg_stride, caps, want_slot_token=False):
+    """moe_route_top1 for the right-padded prompts of one batched prefill, each routed as a pass of its own: gates fp32 [n * seg_stride, E],
+    segment b = tokens b * seg_stride + i, i < seg_lens[b] (host ints; the rest of a stride is padding, never read), at capacity caps[b], no
+    draws.  Per segment the bits of moe_route_top1 on its rows alone; a kept slot sits behind the rows earlier segments keep for the same
+    expert, in a slab of sum(caps) rows.  -> moe_route_top1's tuple with l_aux [n] (slot_token [E, sum(caps)]: global token per slot)."""
+    return _route_segments("mp_moe_route_top1_segments", 1, gates, None, seg_lens, seg_stride, caps, want_slot_token)
+
+
+def moe_route_top2_segments(gates, logits, seg_lens, seg_stride, caps):
+    """moe_route_top2 per segment (see moe_route_top1_segments), no noise: entry arrays of length 2T, T = n * seg_stride, l_aux [n]."""
+    return _route_segments("mp_moe_route_top2_segments", 2, gates, logits, seg_lens, seg_stride, caps, False)
+
+
 def gate_noise(n, seed, offset, gumbel, device):
     out = torch.empty(n, dtype=torch.float32, device=device)
     lib().call("mp_gate_noise_f32", _p(out), n, int(seed), int(offset), 1 if gumbel else 0, _stream())
